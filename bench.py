@@ -20,15 +20,18 @@ The only collective is the gather on rank 0.  On one node (the default) every ra
 shared-memory segment that rank 0 maps as well (sniffles_amd.dist.SharedLanding: N PCIe links in parallel) and only the
 layouts are gathered; SNF_BENCH_GATHER=rccl gathers the result blocks over RCCL (dist.gather_results).
 
-At N = 1 the line also carries
+A plain run (usage below) sets up, warms up, times the steps and prints the line; its `roofline` quotes what the timed
+passes themselves measured.  With --full, at N = 1 the line also carries
   wall_clock    one genome end to end through the drop-in boundary: ingest of Lead objects, upload, pass, the SVCall objects
   cpu_baseline  kind "reference": the UNMODIFIED reference (oracle/_ref, byte-compiled by oracle/make_ref.py) on the same 24 signature
                 tables, one process per contig on this box's cores, with vs_baseline; the C oracle beside it (cpu_baseline.port)
   verified / verified_vs_reference   the HIP results of the exact bench workload compared record by record with the oracle run and
                 with what the reference's CallTask.execute keeps
+  configs       the other BASELINE.json configs, each verified (default config only)
+and at N > 1 (weak scaling) `strong`: the same ranks over ONE genome.
 
-Usage: python bench.py --gpus N --steps K --warmup W      (N > 1: launched by torch.distributed.run)
-Prints ONE JSON line on rank 0.
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]      (N > 1: launched by torch.distributed.run)
+Prints ONE JSON line on rank 0.  --dump-outputs DIR: what the last timed step returned, as DIR/<name>.npy (float64 / float32, finite; NaN / inf mapped in DIR/<name>.nonfinite.npy).
 """
 from __future__ import annotations
 
@@ -62,6 +65,11 @@ def main():
                     help="what a pass returns to the host: execute = what the reference's CallTask.execute returns (QC-passing calls, "
                          "per task sorted by position, parallel.py:265-271), filtered / sorted / compacted on the device; candidates = "
                          "every candidate record (what Task.finalize_candidates returns; the --snf shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: wall clock, CPU baselines, the checks against the oracle and the reference, the "
+                         "other configs, the lone-pass and read-index reference points, the PCIe roof, the strong-scaling run (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float64 / float32, at most 64 MB in all)")
     ap.add_argument("--no-configs", action="store_true", help="skip the compact block of the other BASELINE configs (default run only)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the all-cores oracle run (and with it --verify)")
     ap.add_argument("--no-verify", action="store_true")
@@ -129,10 +137,10 @@ def main():
         out = run_calling(ctx)
         # N > 1, default (weak) scaling: the SAME line also carries the strong-scaling value - ONE genome over the N ranks (north_star's
         # "30x whole genome at 1/2/4/8 MI355X") - measured by a second run of the same command's ranks over the contig-set queue
-        if world > 1 and args.scaling == "weak" and os.environ.get("SNF_BENCH_NO_STRONG") != "1":
+        if world > 1 and args.full and args.scaling == "weak" and os.environ.get("SNF_BENCH_NO_STRONG") != "1":
             import copy
             a2 = copy.copy(args)
-            a2.scaling, a2.no_cpu_baseline, a2.no_wall_clock, a2.no_configs = "strong", True, True, True
+            a2.scaling, a2.no_cpu_baseline, a2.no_wall_clock, a2.no_configs, a2.dump_outputs = "strong", True, True, True, None
             try:
                 out2 = run_calling(dict(ctx, args=a2))
                 if rank == 0:
@@ -148,10 +156,58 @@ def main():
             except Exception as e:  # noqa: BLE001 - the weak line stands on its own
                 if rank == 0:
                     out["strong"] = dict(error=f"{type(e).__name__}: {str(e)[:400]}")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx.get("outputs") or {})
     if rank == 0:
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64_000_000        # "64 MB" in either reading
+
+
+def result_arrays(res) -> dict:
+    """The arrays of a result block (abi.Result, or the gathered block on rank 0) by name: one per record field (`calls.cov`: one
+    column per entry), the read-name and ALT pools, the per-task arrays."""
+    out = {}
+    calls = getattr(res, "calls", None)
+    if calls is not None:
+        for f in calls.dtype.names:
+            if f.startswith("_pad"):
+                continue
+            out["calls." + f] = calls[f]
+    for k in ("rnames", "alt_pool", "task_status", "task_call_off", "coverage_average_total", "task_ids"):
+        a = getattr(res, k, None)
+        if a is not None:
+            out[k] = a
+    return out
+
+
+def dump_outputs(d, arrays) -> None:
+    """DIR/<name>.npy per array: float64 (float32 for byte arrays), exactly the values returned, every value finite.  A floating-point
+    field (NaN = "absent" in `stdev_len`, `vaf`) is written with 0 where it is not finite, beside DIR/<name>.nonfinite.npy: 0 finite,
+    1 NaN, 2 +inf, 3 -inf.  Above DUMP_BYTES in all, every array is cut to the same fraction of its rows, chosen by a fixed seed (the
+    same rows wherever the lengths are the same, so a field and its .nonfinite stay aligned)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind == "f":
+            a = a.astype(np.float64)
+            conv[name + ".nonfinite"] = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1.0, 2.0, 3.0], 0.0).astype(np.float32)
+            conv[name] = np.where(np.isfinite(a), a, 0.0)
+            continue
+        conv[name] = a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    frac = min(1.0, DUMP_BYTES * 0.98 / total) if total else 1.0
+    for name, a in conv.items():
+        if frac < 1.0 and len(a):
+            keep = max(1, int(len(a) * frac))
+            idx = np.sort(np.random.default_rng(12345).choice(len(a), size=keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ======================================================================================================== configs 0-3
@@ -551,6 +607,11 @@ def run_calling(ctx):
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        # what the last timed pass returned (every handle runs the same input): handle 0's block, or the block gathered on rank 0
+        import numpy as np
+        res_last = gathered_box[0] if use_dist else batches[0].fetch(1)
+        ctx["outputs"] = {k: np.array(v) for k, v in result_arrays(res_last).items()} if res_last is not None else {}
     served = served_box[0]
     ranks_seen, sets_served = 1, [served]
     if use_dist:              # who took part, and how the device batches of the timed region were spread over the ranks
@@ -564,7 +625,7 @@ def run_calling(ctx):
     timings = batches[0].timings_mean() or batches[0].timings()
     # reference point outside the timed region: the same pass with ONE batch in flight (per-pass latency)
     lat_ms = None
-    if W > 1 and not strong:
+    if args.full and W > 1 and not strong:
         barrier()
         # (the library stages results through HBM while passes overlapped within the last 0.1 s: this is the lone-pass reference point)
         time.sleep(0.25)
@@ -579,7 +640,7 @@ def run_calling(ctx):
     # for the record: the same passes when every call_candidates ALSO rebuilds the read index (sorted read ends, hap prefix
     # counts - the device form of the coverage vector, which the reference builds during extraction and the library at upload)
     ms_with_index = None
-    if world == 1 and not strong and not use_dist and not args.no_wall_clock:
+    if args.full and world == 1 and not strong and not use_dist and not args.no_wall_clock:
         os.environ["SNF_READPREP_EACH_PASS"] = "1"
         extra = [[lib.Batch(cfg, tasks, device=(0 if EMU else local_rank))] for _ in range(W)]
         del os.environ["SNF_READPREP_EACH_PASS"]
@@ -652,7 +713,7 @@ def run_calling(ctx):
         res_one = batches[0].fetch(1) if not use_dist else None
         result_bytes = (len(res_one.calls) * abi.CALL_DTYPE.itemsize + 4 * len(res_one.rnames)
                         + len(res_one.alt_pool)) if res_one is not None else None
-        pcie_peak = pcie_d2h_peak_gbs(torch)
+        pcie_peak = pcie_d2h_peak_gbs(torch) if args.full else None     # (a measurement of its own)
         result_path = dict(bound="pcie",
                            what="bytes of the result block one pass hands to the host (records + read names + ALT bytes of the "
                            + ("calls CallTask.execute keeps" if args.output == "execute" else "candidates")
@@ -660,8 +721,8 @@ def run_calling(ctx):
                            "host memory, over the time of a step; peak = device -> pinned host copy rate measured in this run",
                            bytes_per_pass=result_bytes, records_per_pass=(len(res_one.calls) if res_one is not None else None),
                            achieved=(round(result_bytes / (ms_per_step * 1e-3) / 1e9, 2) if result_bytes else None),
-                           peak=round(pcie_peak, 2), unit="GB/s",
-                           frac=(round(result_bytes / (ms_per_step * 1e-3) / 1e9 / pcie_peak, 4) if result_bytes else None))
+                           peak=(round(pcie_peak, 2) if pcie_peak else None), unit="GB/s",
+                           frac=(round(result_bytes / (ms_per_step * 1e-3) / 1e9 / pcie_peak, 4) if result_bytes and pcie_peak else None))
         # whole pass against the roofline: SURVEY.md 8(d) algorithmic bytes of one pass (72 B/signature + consensus bytes as
         # counted by the kernels + 8 B/read + 20 B/call) over the time of one pass
         cons_bytes = sum(k[2] for k in kern if k[0].startswith(("e45w_consensus", "e4c_copy")))
@@ -741,7 +802,7 @@ def run_calling(ctx):
                                                 "pysam stand-in of the extraction oracle (pinned by the reference's 17 "
                                                 "known-answer reads)"]),
                    roofline=roofline)
-        if world == 1 and not strong and G == 1:
+        if args.full and world == 1 and not strong and G == 1:
             if not args.no_wall_clock:
                 out["wall_clock"] = wall_clock(cfg, tasks, local_rank, task_specs(args, wl, 0, 0, 1), wl["cfg"])
             if not args.no_cpu_baseline:

@@ -428,7 +428,7 @@ def _bench_two_ranks(extra, port, **env_extra):
 
 def test_bench_two_ranks_weak_scaling_emu():
     """The default N > 1 line: results into node-shared memory by every rank's own kernels, layouts gathered."""
-    d = _bench_two_ranks([], 32500 + (os.getpid() % 500))
+    d = _bench_two_ranks(["--full"], 32500 + (os.getpid() % 500))
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["tasks"] == 48 and d["value"] > 0
     assert d["config"]["gathered_on_rank0"]["ranks"] == 2 and d["config"]["gathered_on_rank0"]["records"] == d["config"]["calls"] > 0
     assert "SharedLanding" in d["config"]["parallelism"]
@@ -475,7 +475,8 @@ def test_bench_population_merge_line_emu():
     import json
     import subprocess
     env = dict(os.environ, SNF_BENCH_EMU="1", OMP_NUM_THREADS="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--scale", "0.004", "--samples", "3", "--steps", "1", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--scale", "0.004", "--samples", "3", "--steps", "1", "--warmup", "1",
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -494,3 +495,51 @@ def test_bench_population_merge_line_emu():
         v = d["verified_vs_reference"]
         assert v["ok"] is True and v["differences"] == [] and v["records_compared"] == c["combined_calls"] > 50 and v["contigs_compared"] == 24
         assert c["verified_vs_reference"] is True
+
+
+def test_bench_plain_line_and_dumped_outputs_emu(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (here through the host tier: SNF_BENCH_EMU=1, tiny contigs) times exactly K
+    steps and carries none of the --full legs; `--dump-outputs DIR` writes the last step's result block as float .npy files, the same
+    from run to run."""
+    import json
+    import subprocess
+    env = dict(os.environ, SNF_BENCH_EMU="1", OMP_NUM_THREADS="1")
+
+    def run(d):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--scale", "0.004",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+    d = run(tmp_path / "a")
+    assert d["steps"] == 3 and d["sets_served"] == [3] and d["ms_per_step"] > 0 and d["value"] > 0
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d)
+    assert not {"wall_clock", "cpu_baseline", "verified", "configs"} & set(d)
+    assert d["config"]["ms_per_pass_one_batch_in_flight"] is None
+    run(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"calls.pos.npy", "calls.svtype.npy", "alt_pool.npy", "rnames.npy", "task_call_off.npy"} <= set(names)
+    # float fields use NaN for "absent": written as finite values beside a map of where the non-finite ones were
+    assert {"calls.stdev_len.nonfinite.npy", "calls.vaf.nonfinite.npy", "coverage_average_total.nonfinite.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, b), n
+        total += a.nbytes
+    assert 0 < total <= 64_000_000
+    for f in ("stdev_len", "vaf"):
+        v, code = np.load(tmp_path / "a" / f"calls.{f}.npy"), np.load(tmp_path / "a" / f"calls.{f}.nonfinite.npy")
+        assert set(np.unique(code)) <= {0.0, 1.0} and np.all(v[code != 0] == 0)
+    # the map itself, on values the tiny workload need not produce
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.dump_outputs(str(tmp_path / "c"), {"x": np.array([1.5, np.nan, np.inf, -np.inf, -2.0]), "n": np.array([3, 4], np.int32)})
+    assert np.load(tmp_path / "c" / "x.npy").tolist() == [1.5, 0.0, 0.0, 0.0, -2.0]
+    assert np.load(tmp_path / "c" / "x.nonfinite.npy").tolist() == [0.0, 1.0, 2.0, 3.0, 0.0]
+    assert np.load(tmp_path / "c" / "n.npy").tolist() == [3.0, 4.0] and not os.path.exists(tmp_path / "c" / "n.nonfinite.npy")
+    assert len(np.load(tmp_path / "a" / "calls.pos.npy")) == d["config"]["calls"] > 0

@@ -10,6 +10,8 @@ import time
 
 from tools.bench_common import EMU, REFERENCE_CPYTHON, ROOT, WORKLOADS, dev_sync, set_dev, task_specs
 
+MAX_GPU_PROCS = 16        # processes that may hold the device open at the same time on a shared GPU box
+
 def bind_to_gpu_numa(torch, local_rank):
     """One process per GPU, bound to the CPUs of the NUMA node the GPU hangs off (what a launcher does for every rank): the
     host threads that drive the batches, their pinned buffers and the staging arena then sit next to the PCIe root of the
@@ -48,8 +50,10 @@ def worker_processes(specs, cfg_kw, device):
     # P = 24 columns / api 720 ms with two queues each against 1 219 ms)
     # ... and P = 24 - the pool size the reference's CPU baseline uses - through ONE GPU server process (sniffles_amd.server): two dozen
     # processes that each open the device are time-sliced by the driver (0.4-0.9 s for the genome, whatever bounds the passes in flight)
+    # ... and at most MAX_GPU_PROCS processes with the device open at once, this one included: the largest plan of workers that each
+    # open the device is cut to MAX_GPU_PROCS - 1 (the server's workers do not open it)
     plan = [(4, "columns", "api", 0), (4, "leads", "api", 0), (8, "columns", "api", 2), (8, "leads", "api", 2),
-            (24, "columns", "api", "server"), (24, "leads", "api", "server"), (24, "columns", "api", 2)]
+            (24, "columns", "api", "server"), (24, "leads", "api", "server"), (MAX_GPU_PROCS - 1, "columns", "api", 2)]
     if os.environ.get("SNF_BENCH_WORKERS"):      # e.g. "8" or "4,24"
         want = {int(x) for x in os.environ["SNF_BENCH_WORKERS"].split(",") if x}
         plan = [p for p in plan if p[0] in want]
@@ -316,7 +320,7 @@ def other_configs(ctx) -> dict:
     try:
         t_all = time.time()
         from tools import bench_population
-        a = copy.copy(args); a.config = 4; a.steps = 2; a.warmup = 1
+        a = copy.copy(args); a.config = 4; a.steps = 2; a.warmup = 1; a.dump_outputs = None
         # (the reference leg of the merge on a bounded sample: the whole workload takes two minutes of host time)
         a.reference_sample_contigs = 4
         r = bench_population.run(dict(ctx, args=a))

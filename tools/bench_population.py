@@ -163,10 +163,16 @@ def run(ctx):
     dt = time.perf_counter() - t0
     phases = dict(candstore.last_timing)
     text_fast = text_box[0].buffer.getvalue()
-    t1 = time.perf_counter()
-    one_pass(objects=True)                 # for the record (and as a check): the same records through SVCall objects + write_call
-    objects_ms = (time.perf_counter() - t1) * 1e3
-    text_equal = text_box[0].buffer.getvalue() == text_fast
+    if getattr(args, "dump_outputs", None):
+        import numpy as np
+        ctx["outputs"] = {"vcf_text": np.frombuffer(text_fast, np.uint8).copy()}     # the merged records of the last timed step
+    full = getattr(args, "full", False)
+    objects_ms = text_equal = None
+    if full:
+        t1 = time.perf_counter()
+        one_pass(objects=True)             # for the record (and as a check): the same records through SVCall objects + write_call
+        objects_ms = (time.perf_counter() - t1) * 1e3
+        text_equal = text_box[0].buffer.getvalue() == text_fast
     lib.combine_resolve_batch = real_call
     tt = torch.tensor([dt], dtype=torch.float64, device=ctx.get("ctl_dev", DEV))
     tot = torch.tensor([n_cands, box["calls"]], dtype=torch.int64, device=ctx.get("ctl_dev", DEV))
@@ -194,7 +200,8 @@ def run(ctx):
                            host_phases_ms={k: (round(v * 1e3, 1) if isinstance(v, float) else v) for k, v in phases.items()},
                            output="merged VCF records as text straight from the group table (vcf.VCF.write_merged), sorted by position "
                                   "per contig task",
-                           through_svcall_objects_ms=round(objects_ms, 1), text_equals_object_path=bool(text_equal),
+                           through_svcall_objects_ms=(round(objects_ms, 1) if full else None),
+                           text_equals_object_path=(bool(text_equal) if full else None),
                            vcf_bytes=len(text_fast or ""),
                            rank0=dict(c_abi_call_ms=round(box["abi_s"] * 1e3, 2), kernel_ms=round(kms, 3),
                                       host_ms=round(dt / steps * 1e3 - box["abi_s"] * 1e3, 1), staged_bytes=staged,
@@ -205,7 +212,7 @@ def run(ctx):
                              frac=round(achieved / HBM_PEAK_GBS, 6), traffic=None, kernel_ms=round(kms, 3), algorithmic_bytes=ab,
                              note="bit-parallel Myers blocks: the kernel is VALU-issue bound (integer work, ~25 ops per 64 DP cells), "
                                   "not HBM bound; bytes = lengths of the aligned strings"))
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], ver = cpu_baseline_and_verify(cfg, readers, my_contigs, S, local_rank, args)
         if ver is not None:
             out["verified"] = bool(ver["ok"] and text_equal)      # group assignment vs the oracle AND the text path vs the object path
