@@ -308,7 +308,10 @@ int64_t snf_trim_caches(int device);
 
 /* batch lifecycle -------------------------------------------------------------------
  * replaces: LeadProvider.__init__/record_lead/record_hap_ref/build_leadtab
- * (src/sniffles/leadprov.py:361-472) as the container of one task's signatures. */
+ * (src/sniffles/leadprov.py:361-472) as the container of one task's signatures.
+ * The SNF_* environment switches that shape a handle (csrc/snf_knobs.h: BatchKnobs; README.md lists them) are taken from the
+ * environment AT THIS CALL and hold until snf_batch_destroy: changing the environment afterwards changes nothing for this handle.
+ * The process-wide ones (ProcessKnobs: pacing, caches, the staging arena) are read once, at their first use in the process. */
 int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out);
 /* registers one task; may be called n_tasks times.  The task's arrays are BORROWED until snf_batch_upload returns
  * (nothing is copied here). */

@@ -302,7 +302,7 @@ extern "C" int snf_combine_resolve_batch(const snf_config_t* cfg, int device, co
   const size_t o_stsize = L.add<int32_t>(S), o_stmctg = L.add<int32_t>(S), o_stalo = L.add<int64_t>(S), o_stahi = L.add<int64_t>(S);
   const size_t o_stsrc = L.add<uint8_t>(S), o_stalist = L.add<int32_t>(S), o_bits = L.add<uint64_t>((size_t)w_off[np]);
   const size_t o_order = L.add<int32_t>((size_t)NC), o_carry = L.add<int8_t>((size_t)k_off[np] + 16);
-  const bool thread_form = getenv("SNF_COMBINE_THREAD") != nullptr;
+  const bool thread_form = CombineKnobs().thread_form;
   const size_t o_edscr = L.add<uint64_t>(thread_form ? (size_t)e_off[np] + 16 : 16);
   const size_t o_out = L.add<int32_t>((size_t)NC);
   const size_t o_stats = L.add<unsigned long long>(3 * 64 * 16);

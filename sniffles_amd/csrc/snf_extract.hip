@@ -1170,7 +1170,6 @@ void x_release(std::vector<void*>& pool) { for (void* p : pool) x_free(p); pool.
 // rank of str(value) among the distinct phase sets plus the literal "NULL" (Python str order)
 bool ps_str_less(int64_t a, int64_t b) { return std::to_string(a) < std::to_string(b); }
 
-#define X_WAVES_DEFAULT 4
 template <bool EMIT> void x_launch_wave(int waves, unsigned grid, const ExView& v, int64_t n) {
   if (waves >= 8) hipLaunchKernelGGL((x_wave<EMIT, 8>), dim3(grid), dim3(64), 0, 0, v, n);
   else if (waves >= 6) hipLaunchKernelGGL((x_wave<EMIT, 6>), dim3(grid), dim3(64), 0, 0, v, n);
@@ -1266,6 +1265,7 @@ void pull_result(snf_extract* x) {
 int do_run(snf_extract* x) {
   if (!x->have_input) snf::fail("snf_extract_run before snf_extract_upload");
   x->have_result = false;
+  const ExtractKnobs k;   // this run's switches (snf_knobs.h)
   ExView& v = x->v;
   const int64_t n = x->n_records;
   const size_t N1 = (size_t)n + 1;
@@ -1293,14 +1293,14 @@ int do_run(snf_extract* x) {
   { const unsigned long long init[8] = {none, 0, 0, 0, 0, 0, 0, 0}; x_h2d(v.tot, init, 64); }      // [0] first error, [4] NM summands (x_prep)
 #ifdef SNF_XTRACE
   SNF_HIP(hipMemset(v.xtrace, 0, (size_t)(n ? n : 1) * 16));
-  v.xtrace_emit = getenv("SNF_XTRACE_PASS") && !strcmp(getenv("SNF_XTRACE_PASS"), "emit");
+  v.xtrace_emit = k.xtrace_emit;
 #endif
   float ms_count = 0, ms_emit = 0;
-  const bool thread_form = getenv("SNF_EXTRACT_THREAD") != nullptr;
-  const int waves = getenv("SNF_EXTRACT_WAVES") ? atoi(getenv("SNF_EXTRACT_WAVES")) : X_WAVES_DEFAULT;
+  const bool thread_form = k.thread_form;
+  const int waves = k.waves;
   for (hipEvent_t& e : x->ev) if (!e) SNF_HIP(hipEventCreate(&e));
   hipEvent_t e0 = x->ev[0], e1 = x->ev[1], e2 = x->ev[2], e3 = x->ev[3];
-  const int64_t grid_cap = getenv("SNF_EXTRACT_GRID") ? std::max(1, atoi(getenv("SNF_EXTRACT_GRID"))) : (1 << 22);   // (a capped grid strides: measured, slower - the dispatcher balances unequal records better)
+  const int64_t grid_cap = k.grid_cap;
   const unsigned grid_w = (unsigned)std::min<int64_t>(n > 0 ? n : 1, grid_cap);
   // (every record's summary is initialised by the counting pass itself, whatever becomes of the record)
   SNF_HIP(hipEventRecord(e0, 0));
@@ -1370,7 +1370,7 @@ int do_run(snf_extract* x) {
   SNF_HIP(hipEventElapsedTime(&ms_count, e0, e1)); SNF_HIP(hipEventElapsedTime(&ms_emit, e2, e3));
   x_d2h(nmv, v.nm_out, 8); nmv[1] = (double)tot[4];
 #ifdef SNF_XTRACE
-  if (const char* path = getenv("SNF_XTRACE_OUT")) {
+  if (const char* path = k.xtrace_out.empty() ? nullptr : k.xtrace_out.c_str()) {
     std::vector<uint32_t> t((size_t)n * 4);
     x_d2h(t.data(), v.xtrace, (size_t)n * 16);
     if (FILE* f = fopen(path, "wb")) { fwrite(t.data(), 16, (size_t)n, f); fclose(f); }

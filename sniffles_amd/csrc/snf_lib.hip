@@ -233,8 +233,7 @@ struct HostBuf {
     // SNF_STAGE_ARENA_MB: the arena is never smaller than this.  A process that serves batches of unknown size (sniffles_amd/server.py)
     // reserves for the largest it expects once, at its first upload, instead of growing when that batch arrives: pinning ~0.5 GB takes
     // ~0.15 s, during which every other thread of the process that faults a page waits as well
-    static const size_t floor_b = getenv("SNF_STAGE_ARENA_MB") ? (size_t)atoll(getenv("SNF_STAGE_ARENA_MB")) << 20 : 0;
-    if (bytes < floor_b) bytes = floor_b;
+    if (bytes < process_knobs().stage_arena_floor) bytes = process_knobs().stage_arena_floor;
     if (bytes <= cap && p) return p;
     if (external) fail("the result does not fit the memory given to snf_batch_set_result_memory (" + std::to_string(bytes) + " bytes needed, " + std::to_string(cap) + " given)");
     release();
@@ -262,34 +261,26 @@ struct HostBuf {
 };
 
 struct snf_batch_impl {
+  const BatchKnobs k;             // the handle's SNF_* switches: the environment at snf_batch_create (snf_knobs.h)
   snf_config_t cfg;
   int device = 0;
   hipStream_t stream = nullptr;   // main stream (also the one fetch/sync wait on)
   hipStream_t stream2 = nullptr;  // side stream: read preparation, finalize scalar kernels
-  hipStream_t stream3 = nullptr;  // third stream: the SMALL consensus class and the verbatim copies next to the LARGE class
-  bool stream3_high = false;      // ... created with the device's highest stream priority
+  hipStream_t stream3 = nullptr;  // third stream: the SMALL consensus class and the verbatim copies next to the LARGE class (k.large_prio: highest priority)
   hipStream_t stream4 = nullptr;  // fourth stream: sv ids + supporting read names and their D2H copy (off the coverage / QC chain)
   hipStream_t cur = nullptr;      // stream the LAUNCH / prim_* helpers enqueue on
   int cur_slot = 0;
-  bool fused = false;             // flag -> scan -> emit chains as fused kernel pairs (snf_fused.h); off: rocPRIM scans
+  bool fused = false;             // flag -> scan -> emit chains as fused kernel pairs (snf_fused.h); off (k.fuse off, or > 2^25 leads; set at upload): rocPRIM scans
   bool timing = true;             // HIP events around the heavy kernels (snf_batch_set_timing)
   bool time_all = false;          // SNF_TIME_ALL=1: HIP events around every launch, not only the heavy kernels
   int time_every = 8;             // the event brackets are recorded on every n-th pass of the handle (1: every pass; snf_batch_timing_every):
   bool time_now = true;           //   two records per launch keep the streams from running launches back to back - measured 80 us of a
   uint64_t pass_count = 0;        //   1.29-ms step with two batches in flight when every pass carried them
-  bool timeline = false;          // SNF_TIMELINE=1: print (offset, duration) of every bracketed op of the step to stderr
   bool res_current = false;       // z1_results has run after the last kernel that changes what it publishes
   int64_t* h_rn_total = nullptr;  // pinned (hb_res): see View::res_rn_total
-  int sched_readprep = 1;         // SNF_READPREP: 0 first, 1 enqueued behind d1w (may start at once), 2 after d3_taskoff, 3 starts with d1w
   void (*k_d2w)(const View, int64_t) = nullptr; void (*k_e1w)(const View, int64_t) = nullptr;  // occupancy variants
   int slots_d1w = 8192, slots_d2w = 8192, slots_e1w = 8192, slots_big = 8192;
   int slots_cons_s = 1 << 22, slots_cons_l = 1 << 22, slots_cons_s1 = 65536;   // grid caps of the SMALL / LARGE consensus kernels
-  bool d1_groups = true;          // merge_inner / resplit: small merged clusters eight per wave (snf_wave_refine_g.h); SNF_NO_D1_GROUPS=1: a wave per cluster
-  bool d2_groups = true;          // call_from: small refined clusters several per wave (snf_wave_call_g.h); SNF_NO_D2_GROUPS=1: a wave per cluster
-  int cons_nw = 1;                // waves per SMALL consensus call: 1 = one wave per call (default: single-wave workgroups leave room for the
-                                  // LARGE class next to them - LARGE in place 0.75 -> 0.5 ms, the pass 2.5 % shorter), SNF_CONS_NW=4: four
-  int cons_large_nw = 4;          // SNF_CONS_LARGE_NW: waves per LARGE consensus call (4, 8, 16)
-  int occ_s = 5;                  // SNF_OCC_S: waves/SIMD the SMALL consensus kernel is compiled for (5, 6, 8)
   int read_key_bits = 64;         // significant bits of the read-end sort key
   std::vector<int32_t> h_rend_max; // per task: largest read end (filled by the upload's validation pass)
   bool uploaded = false;
@@ -313,13 +304,10 @@ struct snf_batch_impl {
   // kernels behind their producers (SNF_STAGE_COPY=kernel: z2_stage_copy reads the sizes on the device)
   bool staged = false; bool staged_kernel = false, stage_block_copied = false, stage_alt_copied = false;
   bool graph_failed = false;      // a capture / instantiate error: eager from then on (reported once with SNF_PROF)
-  bool w4_split = false;          // SNF_W4_SPLIT=1 sets it (read when the batch is opened)
   int64_t h_n_big64 = 0;          // windows of more than 64 leads (counted at upload): upper bound of the blocks the large instance of w4s_segment gets
   int64_t h_n_occ = 0; int win_cap = 0;   // window front end: occupied windows (a property of the input, counted at upload), instance of w4 / w6
   bool reads_ready = false;       // the read index (sorted ends, hap prefix counts) of the uploaded tasks exists
   bool cov_avg_ready = false;     // a call_candidates pass has formed coverage.mean() per task
-  bool readprep_each_pass = false; // SNF_READPREP_EACH_PASS=1: rebuild it in every call_candidates (round-1 behaviour)
-  int run_gap = 1000;
   // host side of the inputs: the caller's arrays are BORROWED from snf_batch_add_task until snf_batch_upload returns
   // (validated, staged into pinned memory and copied by the upload); only the scalars are kept afterwards
   std::vector<snf_task_input_t> tasks;
@@ -386,7 +374,7 @@ T* dalloc(snf_batch_impl* b, size_t n) {
   if (b->slab_used + bytes > b->slab_cap) {
     size_t cap = b->slab_next; if (cap < bytes) cap = bytes;
     size_t got = 0;
-    void* cached = getenv("SNF_NO_SLAB_CACHE") ? nullptr : g_slabs.take(b->device, cap, &got);
+    void* cached = !process_knobs().slab_cache ? nullptr : g_slabs.take(b->device, cap, &got);
     if (cached && got <= 2 * cap + ((size_t)256 << 20)) {   // (a much larger slab is left for a batch that needs it)
       b->bufs.push_back({cached, got, true});
       b->slab = (uint8_t*)cached; cap = got;
@@ -404,7 +392,7 @@ T* dalloc(snf_batch_impl* b, size_t n) {
 }
 void dfree_all(snf_batch_impl* b) {
   for (auto& d : b->bufs) {
-    if (d.slab && !getenv("SNF_NO_SLAB_CACHE") && g_slabs.give(b->device, d.p, d.bytes)) continue;   // kept for the next batch
+    if (d.slab && process_knobs().slab_cache && g_slabs.give(b->device, d.p, d.bytes)) continue;   // kept for the next batch
     (void)hipFree(d.p);
   }
   b->bufs.clear();
@@ -720,6 +708,8 @@ void stage_reads(const snf_task_input_t& t, uint8_t* st, const size_t* off, int6
 void enqueue_read_index(snf_batch_impl* b);
 void enqueue_pass_init(snf_batch_impl* b);
 void enqueue_keys(snf_batch_impl* b);
+// coverage samples by the thread-per-call kernel d4_coverage instead of d4s_coverage (launch_coverage)
+bool coverage_per_call(const snf_batch_impl* b) { return b->k.d4_thread || !b->v.wave_path; }
 
 void do_upload(snf_batch_impl* b) {
   SNF_TRACE("snf_batch_upload");
@@ -729,17 +719,19 @@ void do_upload(snf_batch_impl* b) {
   int64_t N = b->h_lead_off.back(), R = b->h_read_off.back(), NTR = (int64_t)b->h_trs.size();
   if (T >= (1 << 16)) fail("too many tasks in one batch (max 65535)");
   if (N >= (int64_t)1 << 31 || R >= (int64_t)1 << 31) fail("batch too large for 32-bit lead/read indices");
-  v.cfg = b->cfg; v.T = T; v.N = N; v.R = R; v.NTR = NTR; v.run_gap = b->run_gap;
-  v.wave_path = getenv("SNF_NO_WAVE") ? 0 : 1;
-  v.prof = getenv("SNF_PROF") ? 1 : 0;
-  v.merge_reread = (getenv("SNF_MERGE_REREAD") && atoi(getenv("SNF_MERGE_REREAD")) != 0) ? 1 : 0;
-  const bool sort64 = getenv("SNF_SORT64") != nullptr;  // tests: force the wide-key sorts
+  v.cfg = b->cfg; v.T = T; v.N = N; v.R = R; v.NTR = NTR;
+  const int gap_base = b->cfg.cluster_merge_bnd > (int)b->cfg.cluster_repeat_h_max ? b->cfg.cluster_merge_bnd : (int)b->cfg.cluster_repeat_h_max;
+  v.run_gap = b->k.run_gap != KNOB_UNSET ? b->k.run_gap : (gap_base > 1000 ? gap_base : 1000);
+  v.wave_path = b->k.wave_path ? 1 : 0;
+  b->fused = b->k.fuse && N <= ((int64_t)1 << 25);
+  v.prof = b->k.prof ? 1 : 0;
+  v.merge_reread = b->k.merge_reread ? 1 : 0;
   {  // lead sort key: (task*8 + svtype) << bin_bits | bin, one more bit marks leads outside their contig (sorted last)
     int64_t max_bins = 1;
     for (auto& t : b->tasks) { int64_t nb = t.contig_len / (b->cfg.cluster_binsize > 0 ? b->cfg.cluster_binsize : 1) + 1; if (nb > max_bins) max_bins = nb; }
     v.key_bin_bits = bits_for((uint64_t)max_bins);
     v.key_nbits = v.key_bin_bits + bits_for((uint64_t)(8 * (T > 0 ? T : 1)));
-    v.key32 = (!sort64 && v.key_nbits + 1 <= 32) ? 1 : 0;
+    v.key32 = (!b->k.sort64 && v.key_nbits + 1 <= 32) ? 1 : 0;
   }
   v.pool_len = b->h_pool_off.back(); v.pool_cap = 2 * v.pool_len + 16;
   v.pool_extra_base = v.pool_len; v.pool_slice = 0;
@@ -747,7 +739,7 @@ void do_upload(snf_batch_impl* b) {
   // much is kept for reservations through the shared counter; in front of it every resident wave of d1w_refine owns a private
   // slice it fills without any atomic (the shared counter is one address: ~10^4 returning atomics per pass queue up in L2 and
   // were a third of that kernel's time).  A wave whose slice is full falls back to the counter.
-  if (b->slots_d1w > 0 && getenv("SNF_NO_POOL_SLICES") == nullptr) {
+  if (b->slots_d1w > 0 && b->k.pool_slices) {
     v.pool_slice = (v.pool_len / b->slots_d1w) & ~(int64_t)15;
     v.pool_extra_base = v.pool_len + v.pool_slice * b->slots_d1w;
     v.pool_cap = v.pool_extra_base + v.pool_len + 16;
@@ -814,7 +806,7 @@ void do_upload(snf_batch_impl* b) {
       for (int64_t p = 0; p < q.seq_pool_len; p += (4 << 20)) items[1].push_back({t, 1, p, p + (4 << 20) < q.seq_pool_len ? p + (4 << 20) : q.seq_pool_len});
     }
     int nth = (int)std::thread::hardware_concurrency(); if (nth > 32) nth = 32; if (nth < 1) nth = 1;
-    if (const char* e = getenv("SNF_UPLOAD_THREADS")) { nth = atoi(e); if (nth < 1) nth = 1; }
+    if (process_knobs().upload_threads) nth = process_knobs().upload_threads;
     std::mutex emu; std::string err;
     std::atomic<int> has_dash{0};
     auto run_items = [&](const std::vector<Item>& its) {
@@ -928,7 +920,7 @@ void do_upload(snf_batch_impl* b) {
     for (int t = 0; t < T; t++) base[t + 1] = base[t] + (uint64_t)(uint32_t)b->h_rend_max[t] + 1;
     rp.t_base = upload_vec(b, base);
     b->read_key_bits = bits_for(base[T]);
-    rp.key32 = (!sort64 && b->read_key_bits <= 32) ? 1 : 0;
+    rp.key32 = (!b->k.sort64 && b->read_key_bits <= 32) ? 1 : 0;
   }
   rp.r_end = v.r_end; rp.r_hp = v.r_hp; rp.r_task = v.r_task; rp.r_start = v.r_start; rp.rk_in = v.rk_in; rp.rv_in = v.rv_in;
   rp.rk_out = v.rk_out; rp.rv_out = v.rv_out; rp.re_sorted = v.re_sorted; rp.re_top = v.re_top; rp.R = R;
@@ -947,11 +939,11 @@ void do_upload(snf_batch_impl* b) {
     const int bs = b->cfg.cluster_binsize > 0 ? b->cfg.cluster_binsize : 1;
     for (int t = 0; t < T; t++) cell_off[(size_t)t + 1] = cell_off[(size_t)t] + (int64_t)SNF_NTYPES * ((int64_t)b->tasks[(size_t)t].contig_len / bs + 1);
     const int64_t cells = cell_off[(size_t)T];
-    if (N > 0 && b->cfg.dev_min_leads_cluster >= 2 && getenv("SNF_NO_PREFILTER") == nullptr && cells < ((int64_t)1 << 36)) {
+    if (N > 0 && b->cfg.dev_min_leads_cluster >= 2 && b->k.prefilter && cells < ((int64_t)1 << 36)) {
       v.prefilter = 1;
       v.t_cell_off = upload_vec(b, cell_off);
       b->pf_words = (((cells >> 19) + 1) << 19) / 16 + 2;   // (whole 2^19-cell blocks: pf_slot permutes inside a block)
-      v.pf_spread = (getenv("SNF_PF_SPREAD") && atoi(getenv("SNF_PF_SPREAD")) == 1) ? 1 : 0;   // (measured: a1_keys 0.146 ms spread / 0.111 adjacent)
+      v.pf_spread = b->k.pf_spread ? 1 : 0;
       v.pf_bm = dalloc<uint32_t>(b, (size_t)b->pf_words);
       dzero(b, v.pf_bm, (size_t)b->pf_words * 4);
       v.pf_key = dalloc<uint64_t>(b, N); v.pf_keep = dalloc<uint32_t>(b, N1); v.pf_scan = dalloc<uint32_t>(b, N1);
@@ -960,7 +952,7 @@ void do_upload(snf_batch_impl* b) {
   }
   // window front end (snf_stage_window.h): same precondition as the prefilter (a one-lead bin can never seed a cluster); the window
   // width is chosen below, once the leads can be counted per window - the arrays are sized for the narrowest window tried
-  const int WIN_W_MAX = getenv("SNF_WIN_BITS_MAX") ? atoi(getenv("SNF_WIN_BITS_MAX")) : 10, WIN_W_MIN = 6;   // (measured on the 30x genome: 10 beats 9 and 8)
+  const int WIN_W_MAX = b->k.win_bits_max, WIN_W_MIN = 6;
   auto win_layout = [&](int W, std::vector<int64_t>& off) {
     const int bs = b->cfg.cluster_binsize > 0 ? b->cfg.cluster_binsize : 1;
     off.assign((size_t)T + 1, 0);
@@ -968,7 +960,7 @@ void do_upload(snf_batch_impl* b) {
     return off[(size_t)T];
   };
   int64_t win_slots_max = 0;
-  const bool front_wanted = v.prefilter && v.wave_path && getenv("SNF_NO_WINFRONT") == nullptr && getenv("SNF_NO_FUSE") == nullptr && N <= ((int64_t)1 << 25);
+  const bool front_wanted = v.prefilter && v.wave_path && b->k.winfront && b->k.fuse && N <= ((int64_t)1 << 25);
   if (front_wanted) {
     std::vector<int64_t> off;
     win_slots_max = win_layout(WIN_W_MIN, off);
@@ -1022,13 +1014,13 @@ void do_upload(snf_batch_impl* b) {
   // 7.6 + 6.8 - and two replayed passes next to each other are 2.5 % SLOWER than two eager ones, 1.67 against 1.63 ms per step).
   // SNF_CHAIN / SNF_GRAPH = 0 / 1 force either way.
   const bool small_batch = N <= 400000;
-  v.chain_on = getenv("SNF_CHAIN") ? (atoi(getenv("SNF_CHAIN")) != 0) : (getenv("SNF_NO_CHAIN") ? 0 : (small_batch ? 1 : 0));
-  b->graph_mode = getenv("SNF_GRAPH") ? (atoi(getenv("SNF_GRAPH")) != 0 ? 2 : 0) : (getenv("SNF_NO_GRAPH") ? 0 : (small_batch ? 2 : 0));
+  v.chain_on = b->k.chain >= 0 ? b->k.chain : (small_batch ? 1 : 0);
+  b->graph_mode = (b->k.graph >= 0 ? b->k.graph != 0 : small_batch) ? 2 : 0;
   v.big_cap = (int64_t)(N1 / 64 + 2); v.big_cnt = dalloc<uint32_t>(b, 3 * 64 * 16); v.big_list = dalloc<int32_t>(b, (size_t)(3 * 64 * v.big_cap));
   v.big_wave = v.wave_path;
-  { const int hn = getenv("SNF_HEAVY_N") ? atoi(getenv("SNF_HEAVY_N")) : 24; v.heavy_n = hn > 8 && hn < 64 ? hn : 0; }      // (0 / out of range: one class, as before)
-  { const int eb = getenv("SNF_E1_BATCH") ? atoi(getenv("SNF_E1_BATCH")) : 64; v.e1_batch = (eb == 2 || eb == 4 || eb == 8 || eb == 16 || eb == 32) ? eb : 64; }
-  v.stage_cap = getenv("SNF_NO_BIG_STAGE") ? 0 : 1;   // x_big<0>: clusters up to SNF_BIG_STAGE_CAP leads are kept in LDS
+  { const int hn = b->k.heavy_n; v.heavy_n = hn > 8 && hn < 64 ? hn : 0; }      // (0 / out of range: one class, as before)
+  { const int eb = b->k.e1_batch; v.e1_batch = (eb == 2 || eb == 4 || eb == 8 || eb == 16 || eb == 32) ? eb : 64; }
+  v.stage_cap = b->k.big_stage ? 1 : 0;
   v.cdesc = dalloc<ConsDesc>(b, N1); v.crl_off = dalloc<int64_t>(b, N1); v.crl_len = dalloc<int32_t>(b, N1); v.aln_kept_w = dalloc<uint8_t>(b, N1);
   for (int k = 0; k < 8; k++) v.cls_list[k] = k == 6 ? nullptr : dalloc<int32_t>(b, N1);
   v.d2cap = (int64_t)(N1 / 64 + 64);
@@ -1045,7 +1037,6 @@ void do_upload(snf_batch_impl* b) {
   v.cons_tab_sz = dalloc<int64_t>(b, N1 + 1);
   v.sz_tab = dalloc<int64_t>(b, N1 + 1); v.sz_aln = dalloc<int64_t>(b, N1 + 1); v.sz_rd = dalloc<int64_t>(b, N1 + 1);
   v.sc_tab = dalloc<int64_t>(b, N1 + 1); v.sc_aln = dalloc<int64_t>(b, N1 + 1); v.sc_rd = dalloc<int64_t>(b, N1 + 1);
-  b->readprep_each_pass = getenv("SNF_READPREP_EACH_PASS") != nullptr;
   const double t_alloc = now_ms();
   if (v.prefilter) {
     // how many leads the prefilter keeps is a property of the input: counted once here (the same three kernels every pass
@@ -1065,7 +1056,7 @@ void do_upload(snf_batch_impl* b) {
     // window width: the widest whose largest window fits the 256-lead instance of the window kernels, else the widest that fits the
     // 1024-lead one; occupied windows and the largest window are properties of the input (counted here, like NS): the passes size
     // their launches on the host
-    int forced = getenv("SNF_WIN_BITS") ? atoi(getenv("SNF_WIN_BITS")) : 0;
+    int forced = b->k.win_bits;
     int best_w = -1; int64_t best_occ = 0, best_max = 0, best_big = 0;
     std::vector<int64_t> off;
     if (forced && (forced < WIN_W_MIN || forced > WIN_W_MAX)) forced = 0;
@@ -1089,11 +1080,10 @@ void do_upload(snf_batch_impl* b) {
       if (v.win_bits != best_w) { v.NW = win_layout(best_w, off); v.win_bits = best_w; v.t_win_off = upload_vec(b, off); dsync(b); }
       v.front = 1; b->h_n_occ = best_occ; b->win_cap = best_max <= 64 ? 64 : best_max <= 256 ? 256 : SNF_WIN_MAXCAP;
       b->h_n_big64 = best_big; v.w4_list = dalloc<int32_t>(b, (size_t)best_big + 64); v.w4_mode = 0;
-      b->w4_split = getenv("SNF_W4_SPLIT") && atoi(getenv("SNF_W4_SPLIT")) != 0;
     }
     if (v.prof) fprintf(stderr, "[SNF_PROF] window front end: %s (W = %d: %lld windows, %lld occupied, largest %lld leads, %lld of more than 64: w4s_segment in %s)\n", v.front ? "on" : "off",
                         v.win_bits, (long long)v.NW, (long long)best_occ, (long long)best_max, (long long)best_big,
-                        (b->w4_split && b->win_cap > 64 && best_big > 0 && best_big * 8 < (N + 63) / 64) ? "two launches" : "one launch");
+                        (b->k.w4_split && b->win_cap > 64 && best_big > 0 && best_big * 8 < (N + 63) / 64) ? "two launches" : "one launch");
   }
   const double t_winsel = now_ms();
   {  // ALT stage output (HBM; every ALT is the sequence of one lead of its cluster, so all of them together fit the pool) and
@@ -1129,7 +1119,7 @@ void do_upload(snf_batch_impl* b) {
     bool any = false;
     for (int t = 0; t < T; t++) {
       const bool masked = b->h_nm_off[(size_t)t + 1] > b->h_nm_off[(size_t)t];
-      if (masked || maxd[(size_t)t] >= 65536 || getenv("SNF_COV_EXACT")) { b->h_cov_exact[(size_t)t] = 1; any = true; }
+      if (masked || maxd[(size_t)t] >= 65536 || b->k.cov_exact) { b->h_cov_exact[(size_t)t] = 1; any = true; }
     }
     if (any) v.t_cov_exact = upload_vec(b, b->h_cov_exact);
   }
@@ -1137,6 +1127,9 @@ void do_upload(snf_batch_impl* b) {
   b->reads_ready = true;
   b->uploaded = true;
   if (v.prof) fprintf(stderr, "[SNF_PROF] read index (sorted ends, hap prefix counts): %.2f ms\n", now_ms() - t_index0);
+  if (v.prof) fprintf(stderr, "[SNF_PROF] forms: %s path, %s scans, coverage by %s, grouped refine %s, grouped call %s\n", v.wave_path ? "wave" : "thread",
+                      b->fused ? "fused" : "rocPRIM", coverage_per_call(b) ? "d4_coverage" : "d4s_coverage", v.wave_path && b->k.d1_groups ? "on" : "off",
+                      v.wave_path && b->k.d2_groups ? "on" : "off");
   if (v.prof) fprintf(stderr, "[SNF_PROF] upload: %.1f ms (stage %.1f, H2D %.1f [%.1f MB], allocations + derived %.1f = packing + arrays %.2f, prefilter count %.2f, "
                               "window width %.2f, read index %.2f; %zu device allocations)\n",
                       now_ms() - t_begin, t_staged - t_begin, t_copied - t_staged, (double)at / 1e6, now_ms() - t_copied, t_alloc - t_copied, t_pfcount - t_alloc,
@@ -1174,20 +1167,16 @@ DevicePacing& pacing_of(const snf_batch_impl* b) { return g_pacing[(b->device >=
 // ms per step (with rule 1) / 0.959-0.961 (without any rule) on one box - and, made the default, 12 of 16 runs at 0.955-0.97 but FOUR at
 // 1.32-1.49 (the passes one after the other) on the next.  The rules: 37 of 40 default runs of that day at 0.94-0.97, three at 1.15-1.19.
 // Not understood in the time left; the rules stay the default.
-bool chain_gate_on() { static const bool g = getenv("SNF_CHAIN_GATE") && atoi(getenv("SNF_CHAIN_GATE")) != 0; return g; }
-int pace_mode() { static const int m = getenv("SNF_PACE") ? atoi(getenv("SNF_PACE")) : 1; return m; }      // 0 off, 1 both rules, 2 copies in turn only, 3 spaced starts only
-bool pace_on() { return pace_mode() == 1 || pace_mode() == 3; }
-bool pace_copy_turn() { return pace_mode() == 1 || pace_mode() == 2; }
-double pace_frac() { static const double f = getenv("SNF_PACE_FRAC") ? atof(getenv("SNF_PACE_FRAC")) : 0.25; return f; }
+bool pace_on() { return process_knobs().pace == 1 || process_knobs().pace == 3; }          // SNF_PACE: 0 off, 1 both rules, 2 copies in turn only, 3 spaced starts only
+bool pace_copy_turn() { return process_knobs().pace == 1 || process_knobs().pace == 2; }
 // GPU slots (SNF_GPU_SLOTS=n, off by default): at most n passes - of any process of this user - drive a device at a time.  The
 // reference's deployment is a pool of worker PROCESSES (one per contig at most: 24); each of them brings its own HIP context, and the
 // hardware schedules a limited number of queues: two dozen processes with four streams each are time-sliced by the driver and a
 // pass that takes a millisecond alone takes tens (profiles/r05_workers_hw_queues.log).  A slot is an exclusive lock on one of n
 // files under /dev/shm, taken when a pass is enqueued and dropped when its result has been waited for: the workers' host work -
 // records into objects - goes on beside the n passes that hold the device.
-int gpu_slots() { static const int n = getenv("SNF_GPU_SLOTS") ? atoi(getenv("SNF_GPU_SLOTS")) : 0; return n; }
 int slot_acquire(int device) {
-  const int n = gpu_slots();
+  const int n = process_knobs().gpu_slots;
   if (n <= 0) return -1;
   char path[160];
   const int start = (int)((unsigned)getpid() % (unsigned)n);
@@ -1211,12 +1200,12 @@ void pass_begins(snf_batch_impl* b) {
   DevicePacing& P = pacing_of(b);
   const bool other = P.passes_in_flight.fetch_add(1) >= 1;
   if (other) P.last_overlap_ms.store((long long)now_ms());
-  if (!pace_on() || chain_gate_on()) { b->pass_start_ms = now_ms(); return; }
+  if (!pace_on() || process_knobs().chain_gate) { b->pass_start_ms = now_ms(); return; }
   double wait = 0.0;
   {
     std::lock_guard<std::mutex> g(P.pace_mu);
     const double now = now_ms();
-    if (other && P.pass_latency_ms > 0.0) wait = P.last_pass_start_ms + pace_frac() * P.pass_latency_ms - now;
+    if (other && P.pass_latency_ms > 0.0) wait = P.last_pass_start_ms + process_knobs().pace_frac * P.pass_latency_ms - now;
     if (wait > 2.0) wait = 2.0;                 // (never more than 2 ms, whatever the history says)
     if (wait < 0.0) wait = 0.0;
     P.last_pass_start_ms = now + wait;          // (the slot is taken; the wait itself happens outside the lock)
@@ -1277,7 +1266,7 @@ void enqueue_read_prep(snf_batch_impl* b) {
   {
   SideStream side(b);
   if (R > 0) {
-    if (b->readprep_each_pass) enqueue_read_index(b);
+    if (b->k.readprep_each_pass) enqueue_read_index(b);
     // Task.coverage_average_total = coverage.mean(): sum of the clipped read lengths (exact) / contig length
     { Scope _s(b, "d5w_covsum", R * 12);
       int64_t grid = (R + 4095) / 4096; if (grid > 2048) grid = 2048;
@@ -1301,8 +1290,7 @@ void enqueue_read_prep(snf_batch_impl* b) {
 // (d4s_coverage, snf_wave_call.h); SNF_D4=thread: the former thread-per-call kernel with its hinted binary searches
 void launch_coverage(snf_batch_impl* b, int64_t N) {
   View& v = b->v;
-  static const bool per_call = getenv("SNF_D4") && strcmp(getenv("SNF_D4"), "thread") == 0;
-  if (per_call || !v.wave_path) { LAUNCH(d4_coverage, v, N, 0); return; }
+  if (coverage_per_call(b)) { LAUNCH(d4_coverage, v, N, 0); return; }
   Scope _s(b, "d4_coverage", 0);
   int64_t grid = (5 * N + 255) / 256; if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(d4s_coverage, dim3((unsigned)grid), dim3(256), 0, b->cur, v, (int64_t)0);
@@ -1313,7 +1301,6 @@ void launch_coverage(snf_batch_impl* b, int64_t N) {
 void enqueue_pass_init(snf_batch_impl* b) {
   View& v = b->v;
   const int64_t N = v.N; const int T = v.T;
-  b->fused = getenv("SNF_NO_FUSE") == nullptr && N <= ((int64_t)1 << 25);
   if (b->fused) {
     int64_t n0 = 8 * (int64_t)T + 8;
     if (TS_SLOTS * v.super_stride > n0) n0 = TS_SLOTS * v.super_stride;
@@ -1367,7 +1354,7 @@ void enqueue_window_front(snf_batch_impl* b) {
   // 30x genome (profiles/ab_r06_19.log): 4 700-4 900 workgroups in flight instead of 3 800-4 000, each 5-10 % slower - the kernel is bound
   // by instruction issue -, 6 % of the blocks go through the list behind a gap: 84.7 against 82.2 us, the step 0.911-0.913 against
   // 0.917-0.939 ms with two passes in flight, 1.344-1.351 against 1.325-1.344 with one.  Not the default.
-  const bool split = b->w4_split && b->win_cap > 64 && b->h_n_big64 > 0 && b->h_n_big64 * 8 < n_blk;
+  const bool split = b->k.w4_split && b->win_cap > 64 && b->h_n_big64 > 0 && b->h_n_big64 * 8 < n_blk;
   {
     Scope* sc = b->time_all ? new Scope(b, "w4s_segment", 0) : nullptr;
     if (split) {
@@ -1399,7 +1386,7 @@ void run_call_candidates(snf_batch_impl* b) {
   begin_pass_timing(b);
   pass_begins(b);
   b->chain_slot = -1;
-  if (chain_gate_on() && !b->capturing) {
+  if (process_knobs().chain_gate && !b->capturing) {
     DevicePacing& P = pacing_of(b);
     std::lock_guard<std::mutex> g(P.pace_mu);
     const unsigned long long my = P.chain_seq++;
@@ -1410,9 +1397,9 @@ void run_call_candidates(snf_batch_impl* b) {
   }
   // SNF_OUT_EXECUTE (set before this call): the names of the supporting reads are only written for the calls that pass QC,
   // once finalize knows them (a stage-0 fetch writes them all, late)
-  v.rn_defer = ((v.out_mode & SNF_OUT_EXECUTE) && !v.cfg.no_qc && getenv("SNF_NO_RN_DEFER") == nullptr && getenv("SNF_NO_FUSE") == nullptr && N <= ((int64_t)1 << 25)) ? 1 : 0;
+  v.rn_defer = ((v.out_mode & SNF_OUT_EXECUTE) && !v.cfg.no_qc && b->k.rn_defer && b->k.fuse && N <= ((int64_t)1 << 25)) ? 1 : 0;
   b->rn_state = v.rn_defer ? 1 : 0;
-  if (b->timeline) SNF_HIP(hipEventRecord(b->ev_base, b->stream));
+  if (b->k.timeline) SNF_HIP(hipEventRecord(b->ev_base, b->stream));
   // fused chains: two-level tile sums cost O(N / 16384) loads per block, fine up to a few 10^7 elements; beyond that
   // (and in the emulation build) the plain device-wide scans are used
   enqueue_pass_init(b);
@@ -1420,7 +1407,7 @@ void run_call_candidates(snf_batch_impl* b) {
   if (v.wave_path && !b->fused) dzero(b, v.d2cnt, sizeof(uint32_t) * 3 * 64 * 16);
   b->finalize_runs = 0;
   fork_mark(b);  // the read-preparation branch may start here, wherever it is enqueued below
-  if (b->sched_readprep == 0) enqueue_read_prep(b);
+  if (b->k.readprep == 0) enqueue_read_prep(b);
   const bool front = v.front && b->fused && N > 0;
   if (front) enqueue_window_front(b); else enqueue_keys(b);
   if (N > 0) {
@@ -1477,8 +1464,8 @@ void run_call_candidates(snf_batch_impl* b) {
     LAUNCH_Q(c4_clusters, v, N, N * 4);
     dzero(b, v.rcflag, sizeof(uint32_t) * (N + 1));
     }
-    if (b->sched_readprep == 3) fork_mark(b);   // mode 3: the read preparation may only start once stages A-C are through
-    if (v.wave_path && b->d1_groups) {
+    if (b->k.readprep == 3) fork_mark(b);   // mode 3: the read preparation may only start once stages A-C are through
+    if (v.wave_path && b->k.d1_groups) {
       // merge_inner / resplit by cluster size (snf_wave_refine_g.h): eight clusters of <= 8 leads per wave, then d1w_refine - a wave
       // per cluster - for what that kernel handed on
       { Scope _s(b, "d1g_refine8", N * 36 / 3);
@@ -1503,7 +1490,7 @@ void run_call_candidates(snf_batch_impl* b) {
       SNF_HIP(hipGetLastError());
     }
   }
-  if (b->sched_readprep == 1 || b->sched_readprep == 3) enqueue_read_prep(b);  // while the long refine kernel keeps the main stream busy
+  if (b->k.readprep == 1 || b->k.readprep == 3) enqueue_read_prep(b);  // while the long refine kernel keeps the main stream busy
   if (N > 0) {
     if (b->fused && v.chain_on) CHAIN(d1bc_rctable, N);
     else if (b->fused) {
@@ -1513,7 +1500,7 @@ void run_call_candidates(snf_batch_impl* b) {
       prim_exscan<uint32_t>(b, v.rcflag, v.rcscan, N + 1, "scan_refined");
       LAUNCH_Q(d1b_rctable, v, N, N * 4);
     }
-    if (v.wave_path && b->d2_groups) {
+    if (v.wave_path && b->k.d2_groups) {
       // call_from by cluster size (snf_wave_call_g.h): eight clusters of <= 8 leads per wave, then two of <= 32 from the list
       // the first kernel left, then d2w_call - a wave per cluster - for what the second handed on
       const bool ph = b->cfg.phase != 0;
@@ -1523,7 +1510,7 @@ void run_call_candidates(snf_batch_impl* b) {
         if (ph) hipLaunchKernelGGL((d2g_call<8, 4, true>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         else hipLaunchKernelGGL((d2g_call<8, 4, false>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         SNF_HIP(hipGetLastError()); }
-      static const bool mid = getenv("SNF_D2_MID") != nullptr;   // A/B: clusters of 9..32 leads two per wave (measured slower than a wave each)
+      const bool mid = b->k.d2_mid;
       if (mid) { Scope _s(b, "d2g_call32", 0);
         if (ph) hipLaunchKernelGGL((d2g_call<32, 4, true>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         else hipLaunchKernelGGL((d2g_call<32, 4, false>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
@@ -1559,7 +1546,7 @@ void run_call_candidates(snf_batch_impl* b) {
   // stage (sv ids, supporting read names, coverage annotation) continues on the side stream, behind the read preparation
   LAUNCH_Q(d3_taskoff, v, tail_threads(v), 0);
   SNF_HIP(hipEventRecord(b->ev_counts, b->stream));
-  if (b->sched_readprep == 2) enqueue_read_prep(b);
+  if (b->k.readprep == 2) enqueue_read_prep(b);
   fork_mark(b);
   if (b->fused) {
     {  // sv ids + supporting read names: own stream (nothing on the coverage -> QC -> record copy chain waits for them
@@ -1634,7 +1621,7 @@ void enqueue_output_head(snf_batch_impl* b) {
   const bool rn_all = !((v.out_mode & SNF_OUT_EXECUTE) && !v.cfg.no_qc);
   // deferred names of the kept calls: written by f4w_emit itself, from the leads into the block (no pass over the candidates
   // and no intermediate copy in HBM); everything else (all names wanted, the thread form) takes the late kernel
-  const bool rn_src = b->rn_state == 1 && !rn_all && b->fused && NS > 0 && NS <= ((int64_t)1 << 22) * 256 && getenv("SNF_NO_RN_FUSE") == nullptr;
+  const bool rn_src = b->rn_state == 1 && !rn_all && b->fused && NS > 0 && NS <= ((int64_t)1 << 22) * 256 && b->k.rn_fuse;
   if (!rn_src) enqueue_rnames_late(b, rn_all);
   if (b->fused && NS <= ((int64_t)1 << 22) * 256) {
     const unsigned grid = (unsigned)((NS + 255) / 256) > 0u ? (unsigned)((NS + 255) / 256) : 1u;
@@ -1647,7 +1634,7 @@ void enqueue_output_head(snf_batch_impl* b) {
     }
     { Scope _s(b, "f4_emit", 0);
       v.rn_from_src = rn_src ? 1 : 0;
-      static const unsigned f4cap = getenv("SNF_F4_GRID") && atoi(getenv("SNF_F4_GRID")) > 0 ? (unsigned)atoi(getenv("SNF_F4_GRID")) : 2048u;   // experiments
+      const unsigned f4cap = (unsigned)b->k.f4_grid;
       hipLaunchKernelGGL(f4w_emit, dim3(grid < f4cap ? grid : f4cap), dim3(256), 0, b->cur, v, (int64_t)0);
       v.rn_from_src = 0;
       SNF_HIP(hipGetLastError()); }
@@ -1703,29 +1690,28 @@ void run_alt_fallback(snf_batch_impl* b) {
 void enqueue_consensus_wave(snf_batch_impl* b, int64_t g_small, int64_t g_large, int64_t g_copy) {
   SNF_TRACE("E4/E5: INS consensus (SMALL / LARGE / verbatim)");
   View& v = b->v;
-  const bool serial = getenv("SNF_SERIAL") != nullptr;  // dev: every ALT kernel alone on the device (isolated timings)
+  const bool serial = b->k.serial;
   // Order of the two consensus classes.  0: LARGE (main stream) NEXT TO SMALL (third stream) - alone on the device SMALL fills the
   // tail of LARGE's unequal calls (one batch in flight: 1.466 ms per step against 1.494 for order 2).  2: LARGE BEHIND SMALL on one
   // stream - next to each other a LARGE workgroup (70 KB of LDS, 4 x 256 VGPRs on one CU at once) only finds room when SMALL's queue
   // of one-wave workgroups runs dry: LARGE spans 0.51 ms in place against 0.22 behind SMALL (SMALL: 0.27 / 0.17), and with a second
   // pass in flight that pass fills the tails instead (two in flight: 1.238 against 1.242).  So: 2 when another pass is in flight on
   // the device, 0 otherwise; SNF_CONS_ORDER forces one (1 = SMALL behind LARGE: slower than both).
-  const int order_env = getenv("SNF_CONS_ORDER") ? atoi(getenv("SNF_CONS_ORDER")) : -1;
-  const int order = order_env >= 0 ? order_env : (pacing_of(b).passes_in_flight.load() > 1 ? 2 : 0);
+  const int order = b->k.cons_order >= 0 ? b->k.cons_order : (pacing_of(b).passes_in_flight.load() > 1 ? 2 : 0);
   auto launch_large = [&]() {
     Scope _s(b, "e45w_consensus_large", 0, true);
     const dim3 gl((unsigned)(g_large < b->slots_cons_l ? g_large : b->slots_cons_l));
-    if (b->cons_large_nw == 16) hipLaunchKernelGGL((K_CONS_LARGE_16W), gl, dim3(1024), 0, b->cur, v, (int64_t)0);
-    else if (b->cons_large_nw == 8) hipLaunchKernelGGL((K_CONS_LARGE_8W), gl, dim3(512), 0, b->cur, v, (int64_t)0);
+    if (b->k.cons_large_nw == 16) hipLaunchKernelGGL((K_CONS_LARGE_16W), gl, dim3(1024), 0, b->cur, v, (int64_t)0);
+    else if (b->k.cons_large_nw == 8) hipLaunchKernelGGL((K_CONS_LARGE_8W), gl, dim3(512), 0, b->cur, v, (int64_t)0);
     else hipLaunchKernelGGL((K_CONS_LARGE), gl, dim3(256), 0, b->cur, v, (int64_t)0);
     SNF_HIP(hipGetLastError());
   };
   auto launch_small = [&]() {
     Scope _s(b, "e45w_consensus_small", 0);
     const dim3 gs((unsigned)(g_small < b->slots_cons_s ? g_small : b->slots_cons_s));
-    if (b->cons_nw == 1) hipLaunchKernelGGL((K_CONS_SMALL_1W), dim3((unsigned)(g_small < b->slots_cons_s1 ? g_small : b->slots_cons_s1)), dim3(64), 0, b->cur, v, (int64_t)0);
-    else if (b->occ_s >= 8) hipLaunchKernelGGL((K_CONS_SMALL(8)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
-    else if (b->occ_s == 6) hipLaunchKernelGGL((K_CONS_SMALL(6)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
+    if (b->k.cons_nw == 1) hipLaunchKernelGGL((K_CONS_SMALL_1W), dim3((unsigned)(g_small < b->slots_cons_s1 ? g_small : b->slots_cons_s1)), dim3(64), 0, b->cur, v, (int64_t)0);
+    else if (b->k.occ_s >= 8) hipLaunchKernelGGL((K_CONS_SMALL(8)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
+    else if (b->k.occ_s == 6) hipLaunchKernelGGL((K_CONS_SMALL(6)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
     else hipLaunchKernelGGL((K_CONS_SMALL(5)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
     SNF_HIP(hipGetLastError());
   };
@@ -1797,10 +1783,9 @@ void run_finalize(snf_batch_impl* b) {
     // and registers the other pass's kernels need; staged, those kernels end at HBM speed and the copy engines' traffic overlaps the
     // other pass's compute (same box, two in flight: 0.945 ms per step against 1.17; one in flight 1.48 against 1.36 - hence the
     // switch).  SNF_STAGE_OUT=1 / 0 force either.  (Not while a pass is captured: a replayed graph keeps the direct stores.)
-    const int stage_env = getenv("SNF_STAGE_OUT") ? atoi(getenv("SNF_STAGE_OUT")) : -1;
+    const int stage_env = b->k.stage_out;
     const bool stage = !(v.out_mode & SNF_OUT_DEVICE) && !b->capturing && (stage_env == 1 || (stage_env < 0 && passes_overlap(b)));
-    const char* copy_env = getenv("SNF_STAGE_COPY");
-    b->staged = stage; b->staged_kernel = stage && copy_env && strcmp(copy_env, "kernel") == 0;
+    b->staged = stage; b->staged_kernel = stage && b->k.stage_copy_kernel;
     b->stage_block_copied = b->stage_alt_copied = false;
     const bool out_hbm = (v.out_mode & SNF_OUT_DEVICE) || stage;
     v.out_pin = out_hbm ? nullptr : (uint8_t*)b->hb_out.p;
@@ -1809,7 +1794,7 @@ void run_finalize(snf_batch_impl* b) {
     // ALT section: an eighth of the input sequence bytes (a 30x genome needs a twentieth); the fetch grows it when a pass overflowed into HBM
     const size_t want_alt = (size_t)(v.pool_len / 8) + ((size_t)1 << 20);
     if (!(v.out_mode & SNF_OUT_DEVICE) && !b->hb_alt.external && b->hb_alt.cap < want_alt) b->hb_alt.ensure(want_alt);
-    const bool alt_hbm = getenv("SNF_ALT_HBM") != nullptr || stage;   // (SNF_ALT_HBM: measurement - only the ALT bytes into HBM, copied at fetch)
+    const bool alt_hbm = b->k.alt_hbm || stage;
     v.alt_pin = ((v.out_mode & SNF_OUT_DEVICE) || alt_hbm) ? nullptr : (uint8_t*)b->hb_alt.p;
     v.alt_pin_cap = ((v.out_mode & SNF_OUT_DEVICE) || alt_hbm) ? 0 : (int64_t)b->hb_alt.cap;
     v.stage_alt_pin = b->staged_kernel ? (uint8_t*)b->hb_alt.p : nullptr; v.stage_alt_cap = b->staged_kernel ? (int64_t)b->hb_alt.cap : 0;
@@ -1918,8 +1903,8 @@ void run_finalize(snf_batch_impl* b) {
 bool pass_graph_ok(snf_batch_impl* b) {
   const View& v = b->v;
   if (b->graph_mode == 1 && pacing_of(b).passes_in_flight.load() > 1) return false;      // (this batch itself is counted)
-  return b->graph_mode && !b->graph_failed && b->have_hist && b->fused && v.front && v.wave_path && !b->timeline && !b->time_all &&
-         v.NS > 0 && !b->readprep_each_pass && getenv("SNF_SERIAL") == nullptr;
+  return b->graph_mode && !b->graph_failed && b->have_hist && b->fused && v.front && v.wave_path && !b->k.timeline && !b->time_all &&
+         v.NS > 0 && !b->k.readprep_each_pass && !b->k.serial;
 }
 void run_pass(snf_batch_impl* b) {
   View& v = b->v;
@@ -1992,7 +1977,7 @@ void destroy_graphs(snf_batch_impl* b) {
 void collect_timings(snf_batch_impl* b) {
   b->timings.clear();
 #ifdef SNF_ITRACE
-  if (getenv("SNF_PROF") && b->v.itrace) {      // per kernel slot: the workgroups' starts and durations of the pass that just ended
+  if (b->k.prof && b->v.itrace) {      // per kernel slot: the workgroups' starts and durations of the pass that just ended
     static const char* nm[SNF_IT_SLOTS] = {"w1_hist", "w3_scatter", "w4s_segment", "w6t_emit", "d1g_refine", "d1w_refine", "d2g_call", "d2w_call", "e3b_offsets",
                                            "e1w_finalize", "cons SMALL", "cons LARGE", "d4s_coverage", "f4w_emit", "cons ROWS", ""};
     std::vector<uint32_t> h((size_t)SNF_IT_SLOTS * SNF_IT_CAP * 2);
@@ -2021,14 +2006,14 @@ void collect_timings(snf_batch_impl* b) {
   }
 #endif
 #ifdef SNF_WG_TRACE
-  if (getenv("SNF_PROF") && b->v.wgtrace) {
+  if (b->k.prof && b->v.wgtrace) {
     const int64_t n = 1 << 19;
     std::vector<unsigned long long> h((size_t)n * 6);
     (void)hipMemcpy(h.data(), b->v.wgtrace, h.size() * 8, hipMemcpyDeviceToHost);
     (void)hipMemset(b->v.wgtrace, 0, h.size() * 8);
     bool any_wg = false;
     for (int64_t i = 0; i < n && !any_wg; i++) any_wg = h[2 * i + 1] != 0;
-    if (const char* path = any_wg ? getenv("SNF_WG_TRACE_FILE") : nullptr) {   // every workgroup: class, start, duration (100 MHz ticks), L, others, phases, HW_ID, XCC_ID
+    if (const char* path = any_wg && !b->k.wg_trace_file.empty() ? b->k.wg_trace_file.c_str() : nullptr) {   // every workgroup: class, start, duration (100 MHz ticks), L, others, phases, HW_ID, XCC_ID
       if (FILE* f = fopen(path, "w")) {
         for (int64_t i = 0; i < n; i++) { const unsigned long long m = h[2 * i + 1]; if (!m) continue;
           fprintf(f, "%d %llu %llu %d %d %llu %llu %llu\n", (int)((m >> 28) & 15), h[2 * i], m >> 32, (int)(m & 0xffff), (int)((m >> 16) & 0xff), h[2 * (i + n)], h[2 * (i + n) + 1], h[2 * (i + 2 * n)]); }
@@ -2061,12 +2046,12 @@ void collect_timings(snf_batch_impl* b) {
   }
 #endif
 #ifdef SNF_C1_PROFILE
-  if (getenv("SNF_PROF")) { const unsigned long long* c = b->h_cnt->c1p; const double w = (double)(c[8] ? c[8] : 1);
+  if (b->k.prof) { const unsigned long long* c = b->h_cnt->c1p; const double w = (double)(c[8] ? c[8] : 1);
     fprintf(stderr, "[SNF_C1_PROFILE] c1_mergeruns, mean us per wave (%llu waves): first node %.2f | next node %.2f criterion %.2f | merge: stores %.2f metrics %.2f movement %.2f | loop exit %.2f tail %.2f; longest wave %.1f us\n",
             c[8], c[0] * 0.01 / w, c[1] * 0.01 / w, c[2] * 0.01 / w, c[3] * 0.01 / w, c[4] * 0.01 / w, c[5] * 0.01 / w, c[6] * 0.01 / w, c[7] * 0.01 / w, c[9] * 0.01); }
 #endif
 #ifdef SNF_CONS_PROFILE
-  if (getenv("SNF_PROF")) {
+  if (b->k.prof) {
     static const char* nm[9] = {"setup+table", "kmers+probes", "chain", "segments", "run filter", "votes", "barrier+vote+store", "longest workgroup", "workgroups"};
     for (int c = 0; c < 2; c++)
       for (int k = 0; k < 9; k++) if (c * 16 + k < 24) fprintf(stderr, "[SNF_CONS_PROFILE] %s %-20s %llu\n", c ? "LARGE" : "SMALL", nm[k], b->h_cnt->dbg[c * 16 + k]);
@@ -2079,7 +2064,7 @@ void collect_timings(snf_batch_impl* b) {
   for (size_t i = 0; i < b->ev_used; i++) {
     float ms = 0;
     if (hipEventElapsedTime(&ms, b->evs[i].a, b->evs[i].b) != hipSuccess) ms = -1;
-    if (b->timeline) {
+    if (b->k.timeline) {
       float off = 0;
       if (hipEventElapsedTime(&off, b->ev_base, b->evs[i].a) != hipSuccess) off = -1;
       fprintf(stderr, "[SNF_TIMELINE] %9.1f %8.1f  %s\n", off * 1e3, ms * 1e3, b->evs[i].name);
@@ -2633,7 +2618,7 @@ struct StreamPool {
     {
       std::lock_guard<std::mutex> g(mu);
       auto& v = (high ? idle_hi : idle)[device & 63];
-      if (v.size() < 32 && !getenv("SNF_NO_STREAM_POOL")) { v.push_back(s); return; }
+      if (v.size() < 32 && process_knobs().stream_pool) { v.push_back(s); return; }
     }
     (void)hipStreamDestroy(s);
   }
@@ -2679,13 +2664,9 @@ int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out) {
     SNF_HIP(hipSetDevice(device));
     auto b = std::make_unique<snf_batch_impl>();
     b->cfg = *cfg; b->device = device;
-    const char* g = getenv("SNF_RUN_GAP");
-    int base = cfg->cluster_merge_bnd > (int)cfg->cluster_repeat_h_max ? cfg->cluster_merge_bnd : (int)cfg->cluster_repeat_h_max;
-    b->run_gap = g ? atoi(g) : (base > 1000 ? base : 1000);
     b->stream = g_streams.take(b->device);
     b->stream2 = g_streams.take(b->device);
-    b->stream3_high = getenv("SNF_LARGE_PRIO") != nullptr && atoi(getenv("SNF_LARGE_PRIO")) != 0;
-    b->stream3 = g_streams.take(b->device, b->stream3_high);
+    b->stream3 = g_streams.take(b->device, b->k.large_prio);
     b->stream4 = g_streams.take(b->device);
     SNF_HIP(hipEventCreateWithFlags(&b->ev_join4, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_e3, hipEventDisableTiming));
@@ -2701,15 +2682,15 @@ int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out) {
        // workgroup a partial second round doubles the kernel time); since the grouped kernels take the small clusters, what the
        // wave-per-cluster kernels walk is a list of a few unequal items per wave, and the dispatcher balances those better than a
        // stride does: same box, two alternations, 0.937 ms per step against 0.955 (x4: 0.934; one in flight 1.35 against 1.37)
-      const int mult = getenv("SNF_GRID_MULT") ? atoi(getenv("SNF_GRID_MULT")) : 2;
-      const int o2 = getenv("SNF_OCC_D2") ? atoi(getenv("SNF_OCC_D2")) : 5;   // <6> and <8> spill (36 / 100 B of scratch); <5> does not and is as fast
-      const int o1 = getenv("SNF_OCC_E1") ? atoi(getenv("SNF_OCC_E1")) : 5;
+      const int mult = b->k.grid_mult;
+      const int o2 = b->k.occ_d2;
+      const int o1 = b->k.occ_e1;
       b->k_d2w = pick_d2w(o2, b->cfg.phase != 0);
       b->k_e1w = o1 == 6 ? e1w_finalize<6> : o1 == 5 ? e1w_finalize<5> : e1w_finalize<4>;  // <8> trips a register-allocation bug of this hipcc
       const DevInfo di = device_info(b->device, o2, o1, b->k_d2w, b->k_e1w);
       const int cus = di.cus;
       int nb = 0;
-      const int div = getenv("SNF_GRID_DIV") && atoi(getenv("SNF_GRID_DIV")) > 0 ? atoi(getenv("SNF_GRID_DIV")) : 1;   // experiments: a fraction of the resident set (room for the other pass in flight)
+      const int div = b->k.grid_div;
       if (di.nb_d1w > 0) b->slots_d1w = di.nb_d1w * cus * mult / div;
       if (di.nb_d2w > 0) b->slots_d2w = di.nb_d2w * cus * mult / div;
       if (di.nb_e1w > 0) b->slots_e1w = di.nb_e1w * cus * mult / div;
@@ -2718,25 +2699,17 @@ int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out) {
       // or claimed calls from a counter (0.498 / 0.382 ms) - against 0.286 / 0.306 ms for plain grids.  SNF_CONS_GRID_MULT=k
       // caps the grid at k x the resident workgroups (the kernels stride) for experiments.
       b->slots_cons_s = b->slots_cons_l = 1 << 22;
-      if (const char* e = getenv("SNF_CONS_GRID_MULT")) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (K_CONS_SMALL(5)), 256, 0) == hipSuccess && nb > 0) b->slots_cons_s = nb * cus * atoi(e);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (K_CONS_LARGE), 256, 0) == hipSuccess && nb > 0) b->slots_cons_l = nb * cus * atoi(e);
+      if (const int m = b->k.cons_grid_mult; m != KNOB_UNSET) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (K_CONS_SMALL(5)), 256, 0) == hipSuccess && nb > 0) b->slots_cons_s = nb * cus * m;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (K_CONS_LARGE), 256, 0) == hipSuccess && nb > 0) b->slots_cons_l = nb * cus * m;
       }
-      b->slots_cons_s1 = 65536;
-      if (const char* e = getenv("SNF_CONS_SMALL_GRID")) { if (atoi(e) > 0) b->slots_cons_s1 = atoi(e); }   // experiments: the one-wave SMALL kernel strides beyond this many workgroups
+      b->slots_cons_s1 = b->k.cons_small_grid;
       b->slots_big = ((32 * cus) / 64) * 64; if (b->slots_big < 64) b->slots_big = 64;   // x_big: a multiple of its 64 stripes
-      if (getenv("SNF_PROF")) fprintf(stderr, "[SNF_PROF] resident workgroups: d1w %d d2w %d e1w %d (CUs %d)\n", b->slots_d1w, b->slots_d2w, b->slots_e1w, cus);
+      if (b->k.prof) fprintf(stderr, "[SNF_PROF] resident workgroups: d1w %d d2w %d e1w %d (CUs %d)\n", b->slots_d1w, b->slots_d2w, b->slots_e1w, cus);
     }
-    b->timing = getenv("SNF_NO_TIMING") == nullptr;
-    b->timeline = getenv("SNF_TIMELINE") != nullptr;
-    if (const char* e = getenv("SNF_TIME_EVERY")) b->time_every = atoi(e) < 0 ? 0 : atoi(e);
-    b->time_all = getenv("SNF_TIME_ALL") != nullptr || b->timeline;
-    if (const char* e = getenv("SNF_OCC_S")) b->occ_s = atoi(e);
-    if (const char* e = getenv("SNF_CONS_NW")) b->cons_nw = atoi(e);
-    b->d2_groups = getenv("SNF_NO_D2_GROUPS") == nullptr;
-    b->d1_groups = getenv("SNF_NO_D1_GROUPS") == nullptr;
-    if (const char* e = getenv("SNF_CONS_LARGE_NW")) b->cons_large_nw = atoi(e);
-    if (const char* e = getenv("SNF_READPREP")) b->sched_readprep = atoi(e);
+    b->timing = b->k.timing;
+    b->time_every = b->k.time_every < 0 ? 0 : b->k.time_every;
+    b->time_all = b->k.time_all || b->k.timeline;
     *out = reinterpret_cast<snf_batch_t*>(b.release());
   })
 }
@@ -2801,7 +2774,7 @@ void snf_batch_destroy(snf_batch_t* bb) {
   b->ext_ranges.clear();
   if (b->stream) g_streams.give(b->device, b->stream);   // (synchronised above)
   if (b->stream2) g_streams.give(b->device, b->stream2);   // (synchronised above)
-  if (b->stream3) g_streams.give(b->device, b->stream3, b->stream3_high);   // (synchronised above)
+  if (b->stream3) g_streams.give(b->device, b->stream3, b->k.large_prio);   // (synchronised above)
   if (b->stream4) g_streams.give(b->device, b->stream4);   // (synchronised above)
   if (b->ev_join4) (void)hipEventDestroy(b->ev_join4);
   delete b;

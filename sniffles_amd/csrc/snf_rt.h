@@ -13,6 +13,7 @@
 #include <dlfcn.h>
 
 #include <hip/hip_runtime.h>
+#include "snf_knobs.h"
 #define SNF_HD __host__ __device__ __forceinline__
 #define SNF_D __device__ __forceinline__
 
@@ -35,7 +36,7 @@ struct Error {
   } while (0)
 
 // ---- roctx ranges (the reference has per-stage debug output; here the stages of a pass show up as named
-// ranges in rocprofv3 --marker-trace / omnitrace).  libroctx64 is looked up at run time and only when SNF_ROCTX=1, so the
+// ranges in rocprofv3 --marker-trace / omnitrace).  libroctx64 is looked up at run time and only when SNF_ROCTX=1 (snf_knobs.h), so the
 // library has no link-time dependency on the tracer and the default path pays one predictable branch per range.
 struct Roctx {
   typedef int (*push_t)(const char*); typedef int (*pop_t)();
@@ -43,8 +44,7 @@ struct Roctx {
   static Roctx& get() {
     static Roctx r = [] {
       Roctx q;
-      const char* e = getenv("SNF_ROCTX");
-      if (e && atoi(e) != 0) {
+      if (process_knobs().roctx) {
         void* h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
         if (!h) h = dlopen("libroctx64.so.4", RTLD_NOW | RTLD_GLOBAL);
         if (h) { q.push = (push_t)dlsym(h, "roctxRangePushA"); q.pop = (pop_t)dlsym(h, "roctxRangePop"); }

@@ -190,11 +190,13 @@ def _with_reads(ti, n_reads, seed, max_len=1500):
 
 
 @pytest.mark.parametrize("d4", [None, "thread"])
-def test_coverage_samples_over_large_read_tables(d4, simt, oracle_mod, monkeypatch):
+def test_coverage_samples_over_large_read_tables(d4, simt, oracle_mod, monkeypatch, capfd):
     """The five coverage samples of every call (d4s_coverage: a thread per sample, rank queries as a 16-ary descent over sampled
     levels of the GLOBAL read arrays, snf_exact.h::rank_upper_16ary) on read tables that reach every level: task segments that start
     at unaligned offsets, cross 4096- and 65536-entry boundaries, hold fewer than 16 reads, end in a partial node; runs of equal
-    starts; samples left and right of every read.  SNF_D4=thread: the former thread-per-call kernel stays selectable."""
+    starts; samples left and right of every read.  SNF_D4=thread: the former thread-per-call kernel stays selectable - the handle
+    reports the kernel it launches (the [SNF_PROF] forms line of the upload), the switch is not taken on trust."""
+    monkeypatch.setenv("SNF_PROF", "1")
     if d4:
         monkeypatch.setenv("SNF_D4", d4)
     sizes = (3, 4090, 9, 70_001, 12_345, 17)
@@ -203,6 +205,8 @@ def test_coverage_samples_over_large_read_tables(d4, simt, oracle_mod, monkeypat
     tis[3].read_end[2000:2300] = int(tis[3].read_start[2299]) + 100   # ... and of equal ends
     cfg = SnifflesConfig()
     got = records.records(run(simt.lib(), cfg, tis, True), tis, "final")
+    forms = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("[SNF_PROF] forms:")]
+    assert len(forms) == 1 and ("coverage by d4_coverage," if d4 else "coverage by d4s_coverage,") in forms[0], forms
     assert got == records.records(oracle_mod.run(cfg, tis, True), tis, "final")
     assert sum(len(g) for g in got) > 50
 

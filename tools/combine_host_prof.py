@@ -40,7 +40,7 @@ def main():
     ap.add_argument("--gpu", action="store_true")
     ap.add_argument("--chunks", default=None, help="comma-separated SNF_COMBINE_CHUNKS values to time one after the other")
     ap.add_argument("--sweep", default=None, help="environment settings to time one after the other on the one population, e.g. "
-                    "SNF_COMBINE_WAVES=8+SNF_COMBINE_HEAVY=1e7,SNF_COMBINE_WAVES=1 (the library reads them at every call)")
+                    "SNF_COMBINE_THREAD=1,SNF_COMBINE_NO_CUT=1+SNF_COMBINE_CHUNKS=2 (the combine entry point and the Python merge read theirs at every call)")
     ap.add_argument("--cache", default=None, help="pickle of the emulated population and group assignment (built when absent)")
     a = ap.parse_args()
     contigs = [(ci, c, max(200000, int(synth.GRCH38[c] * a.scale))) for ci, c in enumerate(synth.CONTIGS)]
