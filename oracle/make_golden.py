@@ -233,6 +233,30 @@ def main_consensus_long():
     print(f"consensus_long_segments: {len(cases_)} problems, {changed} with a consensus that differs from the best read")
 
 
+def main_consensus_class_edges():
+    """Golden vectors for seam B4 on both sides of every edge of cons_class_of (cases.CONS_EDGES): the reference's own
+    consensus.novel_from_reads.  The reads come from the seeded generator of tests/cases.py and are NOT stored (a 65 000-base problem
+    would not fit): per problem the hash of its input, klen, skip, the intended class and the reference's result."""
+    import cases
+    import ref_harness as rh
+    ref = rh.load_reference()
+
+    class L:
+        def __init__(self, seq):
+            self.seq = seq
+
+    out = []
+    for p in cases.consensus_edge_problems():
+        exp = ref.consensus.novel_from_reads(L(p["best"]), [L(o) for o in p["others"]], klen=p["klen"], skip=p["skip"], skip_repetitive=p["skip"])
+        out.append(dict(name=p["name"], input_sha=cases.consensus_problem_sha(p), klen=p["klen"], skip=p["skip"], cls=p["cls"],
+                        best_len=len(p["best"]), n_others=len(p["others"]), expected=exp))
+        print(f"{p['name']:20s} L {len(p['best']):6d}  others {len(p['others']):4d}  skip {p['skip']:4d}  klen {p['klen']}  "
+              f"{sum(a != b for a, b in zip(exp, p['best']))} bases changed")
+    doc = dict(case="consensus_class_edges", n=len(out), problems=out)
+    with gzip.GzipFile(os.path.join(ROOT, "tests", "golden", "consensus_class_edges.json.gz"), "wb", mtime=0) as f:
+        f.write(json.dumps(doc, sort_keys=True, separators=(",", ":")).encode())
+
+
 def main_combine_task(names=None):
     """Goldens for the CombineTask.execute driver: inputs (SNF blocks per sample) and the combined calls it emits."""
     import cases
@@ -479,7 +503,7 @@ if __name__ == "__main__":
     # python oracle/make_golden.py                 -> every fixture family
     # python oracle/make_golden.py vcf sample      -> only these families
     # python oracle/make_golden.py main fuzz_4_2   -> single cases of the `main` / `combine` families
-    FAMILIES = dict(main=main, clusters=main_clusters, regenotype=main_regenotype, combine=main_combine, consensus=main_consensus, consensus_long=main_consensus_long, combine_task=main_combine_task,
+    FAMILIES = dict(main=main, clusters=main_clusters, regenotype=main_regenotype, combine=main_combine, consensus=main_consensus, consensus_long=main_consensus_long, consensus_class_edges=main_consensus_class_edges, combine_task=main_combine_task,
                     bam=main_bam_fixtures, extract=main_extract, snf=main_snf, vcf=main_vcf, sample=main_sample, genotype=main_genotype, population=main_population, genotype_vcf=main_genotype_vcf)
     argv = sys.argv[1:]
     fams = [a for a in argv if a in FAMILIES] or list(FAMILIES)

@@ -297,6 +297,189 @@ def case_single_leads_only():
     return mk_task(leads, _reads(10, 0, 5000), 5000)
 
 
+# ----------------------------------------------------------------------------- size-class ladders
+# One cluster per lead count on both sides of every size class of the cluster kernels (tests/size_classes.py reads the classes from
+# the sources): d1g_refine<8> / d2g_call<8> take clusters of up to 8 leads eight per wave, d1w_refine / d2w_call up to 64 (a lead per
+# lane), SNF_HEAVY_N orders their hand-over lists, x_big<0> keeps up to SNF_BIG_STAGE_CAP leads in LDS, x_big<1/2> up to
+# SNF_BIG_FINAL_CAP rows, the window kernels 64 / 256 / SNF_WIN_MAXCAP leads of a window; the reference's compute_metrics changes
+# above 100 leads.  Clusters lie LADDER_GAP apart, every lead of a cluster in one 100-bp bin (positions within 30 bp), every lead on a
+# read of its own.  tests/test_size_classes.py asserts that the expected calls carry exactly the planned lead counts.
+LADDER_GAP = 20_000
+LADDER_BASE = 50_000
+
+
+def _ladder_pos(c):
+    return LADDER_BASE + c * LADDER_GAP + 10
+
+
+def _ladder_reads(n_clusters, depth=300):
+    L = LADDER_BASE + (n_clusters + 1) * LADDER_GAP
+    return _reads(depth, 0, L) + _reads(40, 0, L // 2, 1) + _reads(25, L // 3, L, 2), L
+
+
+def ladder_plan(svtype):
+    """(lead counts of the ladder's clusters in the order they lie on the contig, leading non-BND cluster or None)."""
+    import size_classes as sc
+    return sc.ladder_sizes(with_window_cap=svtype == "DEL"), (6 if svtype == "BND" else None)
+
+
+def _ladder_lead(svtype, rng, pos, name, i, allele=None, c=0):
+    strand = "+-"[i % 2]
+    p = pos + int(rng.integers(0, 30))
+    if svtype == "DEL":
+        return dict(svtype="DEL", ref_start=p, svlen=-(300 + int(rng.integers(0, 5))), read=name, strand=strand)
+    if svtype == "INS":
+        return dict(svtype="INS", ref_start=p, svlen=len(allele), read=name, strand=strand, seq=_mutate(rng, allele, 0.03))
+    if svtype == "DUP":
+        return dict(svtype="DUP", ref_start=p, svlen=700 + int(rng.integers(0, 5)), read=name, strand=strand, source="SPLIT_SUP")
+    if svtype == "INV":
+        return dict(svtype="INV", ref_start=p, svlen=900 + int(rng.integers(0, 5)), read=name, strand=strand, source="SPLIT_SUP")
+    assert svtype == "BND"
+    return dict(svtype="BND", ref_start=p, read=name, strand=strand, mate=("chr2", 700_000 + 5000 * c + int(rng.integers(0, 30)), True, False))
+
+
+def case_ladder(svtype, max_size=None):
+    """A plain ladder of `svtype` (max_size: only the clusters of at most so many leads).  INS leads carry mutated copies of a 120-bp allele (registered with consensus_max_reads_bin above the
+    largest cluster, so every lead keeps its sequence and the consensus runs with n - 1 other reads); the BND ladder lies behind a DEL
+    cluster (a task of BNDs only is the reference's UnboundLocalError, case_bnd_first_error)."""
+    rng = np.random.default_rng([77, SVT[svtype]])
+    sizes, lead_in = ladder_plan(svtype)
+    if max_size is not None:
+        sizes = [n for n in sizes if n <= max_size]
+    allele = _rng_seq(rng, 120)
+    leads = []
+    if lead_in:
+        leads += [dict(svtype="DEL", ref_start=3000 + i % 3, svlen=-400, read=f"d{i}", strand="+-"[i % 2]) for i in range(lead_in)]
+    for c, n in enumerate(sizes):
+        for i in range(n):
+            leads.append(_ladder_lead(svtype, rng, _ladder_pos(c), f"{svtype[0].lower()}{c}_{i}", i, allele, c))
+    reads, L = _ladder_reads(len(sizes))
+    return mk_task(leads, reads, L)
+
+
+# ... sizes after the refinement that differ from the merged cluster's: the refine kernels are picked by the merged size, the call
+# kernels by the refined one.  RESPLIT: one merged cluster of a + b leads in two svlen modes that `resplit` takes apart;
+# FUSE: clusters in which `k` reads carry two pieces each that merge_inner fuses (pieces of half the length: the fused lead falls into the
+# svlen bin of the others), so n + k merged leads become n.
+def refined_plan():
+    import size_classes as sc
+    t = sc.thresholds()
+    W, G, S, F = sc.WAVE, sc.GROUP, t["big_stage_cap"], t["big_final_cap"]
+    resplit = [(W, 1), (W, W), (G, G), (G, 1), (S, 1), (F, 1)]
+    fuse = [(G, 1), (G - 1, 3), (W, 1), (W - 1, 4), (S, 1), (S - 1, 5), (W, W), (G, G)]      # (refined leads, reads with two pieces)
+    return resplit, fuse
+
+
+def case_ladder_refined(svtype):
+    """svtype INS / DEL: see refined_plan.  BND: resplit_bnd takes clusters apart by mate contig (two mate contigs, a + b leads)."""
+    rng = np.random.default_rng([78, SVT[svtype]])
+    resplit, fuse = refined_plan()
+    allele = _rng_seq(rng, 120)
+    allele2 = _rng_seq(rng, 600)
+    leads = []
+    c = 0
+    if svtype == "BND":
+        leads += [dict(svtype="DEL", ref_start=3000 + i % 3, svlen=-400, read=f"d{i}", strand="+-"[i % 2]) for i in range(6)]
+        for a, b in resplit:
+            for i in range(a + b):
+                mate = ("chr2", 700_000 + int(rng.integers(0, 30)), True, False) if i % (a + b) < a else ("chr7", 90_000 + int(rng.integers(0, 30)), True, False)
+                leads.append(dict(svtype="BND", ref_start=_ladder_pos(c) + int(rng.integers(0, 30)), read=f"b{c}_{i}", strand="+-"[i % 2], mate=mate))
+            c += 1
+        reads, L = _ladder_reads(c)
+        return mk_task(leads, reads, L)
+    sign = -1 if svtype == "DEL" else 1
+    for a, b in resplit:
+        order = rng.permutation(a + b)           # the two modes interleaved in arrival order
+        for i in order:
+            big = i >= a
+            p = _ladder_pos(c) + int(rng.integers(0, 30))
+            d = dict(svtype=svtype, ref_start=p, svlen=sign * (600 if big else 120), read=f"s{c}_{i}", strand="+-"[int(i) % 2])
+            if svtype == "INS":
+                d["seq"] = _mutate(rng, allele2 if big else allele, 0.03)
+            leads.append(d)
+        c += 1
+    for n, k in fuse:
+        for i in range(n):
+            p = _ladder_pos(c) + int(rng.integers(0, 30))
+            q = 3000 + 13 * i
+            st = "+-"[i % 2]
+            if i % (n // k) == 0 and i // (n // k) < k:      # two pieces on one read, close on the reference and on the read
+                s = _mutate(rng, allele, 0.03)
+                d1 = dict(svtype=svtype, ref_start=p, svlen=sign * 60, read=f"f{c}_{i}", strand=st, qry_start=q, qry_end=q + (60 if sign > 0 else 0))
+                d2 = dict(svtype=svtype, ref_start=p + 40, svlen=sign * 60, read=f"f{c}_{i}", strand=st, qry_start=q + 100, qry_end=q + 100 + (60 if sign > 0 else 0))
+                if svtype == "INS":
+                    d1["seq"], d2["seq"] = s[:60], s[60:]
+                leads += [d1, d2]
+            else:
+                d = dict(svtype=svtype, ref_start=p, svlen=sign * 120, read=f"f{c}_{i}", strand=st, qry_start=q, qry_end=q + (120 if sign > 0 else 0))
+                if svtype == "INS":
+                    d["seq"] = _mutate(rng, allele, 0.03)
+                leads.append(d)
+        c += 1
+    reads, L = _ladder_reads(c)
+    return mk_task(leads, reads, L)
+
+
+def phased_long_plan():
+    import size_classes as sc
+    t = sc.thresholds()
+    return sc.around(sc.WAVE) + [t["big_stage_cap"], t["big_stage_cap"] + 1]
+
+
+def case_ladder_phased():
+    """DEL and INS clusters of 63 / 64 / 65 and 160 / 161 leads with `hap` / `ps` set: the phase tally of the wave kernels against the
+    serial bodies - a clear majority, a split between two phase sets, and unphased leads in between."""
+    rng = np.random.default_rng(79)
+    allele = _rng_seq(rng, 120)
+    leads = []
+    c = 0
+    for svtype in ("DEL", "INS"):
+        for n in phased_long_plan():
+            for i in range(n):
+                if c % 3 == 0:
+                    hap, ps = (1, f"P{c}") if i % 8 else (0, "NULL")
+                elif c % 3 == 1:
+                    hap, ps = (1 + i % 2, f"P{c}" if i % 5 else f"Q{c}")
+                else:
+                    hap, ps = (2, f"P{c}") if i < (3 * n) // 4 else (1, f"P{c}")
+                d = _ladder_lead(svtype, rng, _ladder_pos(c), f"p{c}_{i}", i, allele, c)
+                d.update(hap=hap, ps=ps)
+                leads.append(d)
+            c += 1
+    reads, L = _ladder_reads(c, depth=120)
+    return mk_task(leads, reads, L)
+
+
+def case_ladder_long_ins():
+    """INS at long_ins_length (2500) with `leads_long` (clipped leads without a length) beside 63 / 64 / 65 and 160 / 161 leads with one:
+    the support union, SUPPORT_LONG and a consensus over 2.5-kb reads with n - 1 others (see case_long_ins)."""
+    rng = np.random.default_rng(80)
+    allele = _rng_seq(rng, 2500)
+    leads = []
+    for c, n in enumerate(phased_long_plan()):
+        for i in range(n):
+            leads.append(dict(svtype="INS", ref_start=_ladder_pos(c) + int(rng.integers(0, 30)), svlen=2500 + i % 3, read=f"l{c}_{i}",
+                              seq=_mutate(rng, allele, 0.02) + "A" * (i % 3), strand="+-"[i % 2]))
+        for i in range(7):       # clipped: five reads of their own, two that also carry a lead with a length
+            leads.append(dict(svtype="INS", ref_start=_ladder_pos(c) + 35 + i, svlen=None, read=f"k{c}_{i}" if i < 5 else f"l{c}_{i - 5}", strand="+-"[i % 2]))
+    reads, L = _ladder_reads(len(phased_long_plan()), depth=200)
+    return mk_task(leads, reads, L)
+
+
+_ALL_SEQ = dict(consensus_max_reads_bin=2000), ("--consensus-max-reads-bin", "2000")
+LADDERS = {}
+for _t in ("INS", "DEL", "DUP", "INV", "BND"):
+    _kw, _args = _ALL_SEQ if _t == "INS" else ({}, ())
+    LADDERS[f"ladder_{_t.lower()}"] = ((lambda t=_t: case_ladder(t)), dict(_kw), tuple(_args))
+    LADDERS[f"ladder_{_t.lower()}_mosaic"] = ((lambda t=_t: case_ladder(t)), dict(_kw, mosaic=True), tuple(_args) + ("--mosaic",))
+for _t in ("INS", "DEL", "BND"):
+    _kw, _args = _ALL_SEQ if _t == "INS" else ({}, ())
+    LADDERS[f"ladder_refined_{_t.lower()}"] = ((lambda t=_t: case_ladder_refined(t)), dict(_kw), tuple(_args))
+LADDERS["ladder_phased"] = (case_ladder_phased, dict(_ALL_SEQ[0]), _ALL_SEQ[1])
+LADDERS["ladder_phased_mosaic"] = (case_ladder_phased, dict(_ALL_SEQ[0], mosaic=True), _ALL_SEQ[1] + ("--mosaic",))
+LADDERS["ladder_long_ins"] = (case_ladder_long_ins, dict(_ALL_SEQ[0]), _ALL_SEQ[1])
+
+
 HAND = {
     "resplit_wrap": (case_resplit_wrap, {}, ()),
     "merge_index_rule": (case_merge_index_rule, {}, ()),
@@ -320,6 +503,7 @@ HAND = {
     # --dev-no-resplit keeps BND clusters with mixed mate contigs whole: SUPPORT counts the reads of the selected mate contig,
     # RNAMES the reads of the whole cluster (sv.py:555 vs 636)
     "bnd_mixed_mates_no_resplit": (case_bnd_stale_end, dict(dev_no_resplit=True), ("--dev-no-resplit",)),
+    **LADDERS,
 }
 
 # seeded synthetic (SURVEY.md 8d shapes, shrunk contigs) --------------------------------------------
@@ -402,6 +586,62 @@ HAND_COV = {
     "deep_wrap_cov": (case_deep_wrap_cov, {}, ()),
 }
 ALL = {**HAND, **SYNTH, **FUZZ, **FUZZ_DEV, **HAND_COV}
+
+
+# ---------------------------------------------------------------------------------------------- consensus class edges
+# Problems on both sides of every edge of cons_class_of (snf_stage_final.h): (name, L of the best read, other reads, sampling step, k-mer
+# length, intended class: 1 SMALL, 2 LARGE, 4 ROWS, 0 the thread kernels).  Long problems have few other reads, crowded ones are short.
+# tests/test_size_classes.py asserts every intended class against the rule as tests/size_classes.py reads it from the sources.
+CONS_EDGES = [
+    ("small_npos_120", 366, 8, 3, 6, 1), ("small_npos_121", 367, 8, 3, 6, 2),
+    ("small_len_384", 384, 8, 4, 6, 1), ("small_len_385", 385, 8, 4, 6, 2),
+    ("small_others_64", 200, 64, 3, 6, 1), ("small_others_65", 200, 65, 3, 6, 2),
+    ("small_skip_7", 300, 9, 7, 6, 1), ("small_skip_8", 300, 9, 8, 6, 2),
+    ("large_npos_500", 1506, 6, 3, 6, 2), ("large_npos_501", 1507, 6, 3, 6, 0),
+    ("large_others_254", 300, 254, 3, 6, 2), ("large_others_255", 300, 255, 3, 6, 4),
+    ("large_len_8192", 8192, 5, 17, 6, 2), ("large_len_8193", 8193, 5, 17, 6, 4),
+    ("rows_others_512", 200, 512, 3, 6, 4), ("rows_others_513", 200, 513, 3, 6, 0),
+    ("rows_len_64999", 64999, 5, 130, 6, 4), ("rows_len_65000", 65000, 5, 130, 6, 0),
+    ("klen_7", 300, 9, 3, 7, 1), ("klen_8", 300, 9, 3, 8, 0),
+    ("words_skip_15", 3000, 7, 15, 6, 2), ("words_skip_16", 3000, 7, 16, 6, 2), ("words_skip_17", 3000, 7, 17, 6, 2),
+    ("words_skip_23", 3000, 7, 23, 6, 2), ("words_skip_24", 3000, 7, 24, 6, 2),
+]
+
+
+def consensus_edge_problems(balanced=False):
+    """[dict(name, best, others, klen, skip, cls)] for CONS_EDGES, seeded per problem.  The truth is random ACGT; the best read carries
+    4 % substitutions of its own (the vote corrects them: the expected string differs from the best read), every other read 2 %
+    substitutions and, three reads in four, a short deletion and a short insertion.  balanced: deletion and insertion of equal length
+    in every read (all reads as long as the best one - inside a whole pass any of them may become the best read)."""
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    out = []
+    for k, (name, L, n_others, skip, klen, cls) in enumerate(CONS_EDGES):
+        rng = np.random.default_rng([20261017, k])
+        truth = acgt[rng.integers(0, 4, L)]
+
+        def noisy(rate, indel):
+            o = truth.copy()
+            hit = rng.random(L) < rate
+            o[hit] = acgt[rng.integers(0, 4, int(hit.sum()))]
+            if indel:
+                a, b = sorted(int(x) for x in rng.integers(10, L - 10, 2))
+                nd = int(rng.integers(1, 5))
+                ni = nd if balanced else int(rng.integers(1, 5))
+                o = np.concatenate([o[:a], o[a + nd:b], acgt[rng.integers(0, 4, ni)], o[b:]]) if b - a > nd else o
+            return o.tobytes().decode()
+        best = noisy(0.04, False)
+        others = [noisy(0.02, j % 4 != 0) for j in range(n_others)]
+        out.append(dict(name=name, best=best, others=others, klen=klen, skip=skip, cls=cls))
+    return out
+
+
+def consensus_problem_sha(p) -> str:
+    import hashlib
+    h = hashlib.sha256()
+    for s in [p["best"]] + list(p["others"]):
+        h.update(s.encode()); h.update(b"|")
+    h.update(repr((p["klen"], p["skip"])).encode())
+    return h.hexdigest()
 
 
 # multi-sample combine (BASELINE.json configs[4] shape, shrunk): samples share sites, not reads ------------------

@@ -1,0 +1,91 @@
+"""The size thresholds at which the library changes kernel form, read from the sources by regular expression (the way
+tests/test_knobs.py reads the switches), and the ladders t - 1, t, t + 1 the directed cases of tests/cases.py and
+tests/test_size_classes.py are derived from.  A threshold that is no longer found is an error, not a default: a case that
+silently tests the middle of a class is what this module is there to prevent."""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "sniffles_amd", "csrc")
+
+# fixed by the machine / the kernels' shape, not by a named constant: a group of eight in d1g_refine<8> / d2g_call<8>, half a wave, a
+# wave (d1w_refine / d2w_call: a lead per lane; e1w_finalize: SNF_E1_BATCH calls per wave), two waves, the 256-lead window instance,
+# and the reference's own switch in compute_metrics (more than 100 leads)
+GROUP, HALF_WAVE, WAVE, TWO_WAVES, WIN_MID, REF_METRICS = 8, 32, 64, 128, 256, 100
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _one(pattern, text, what):
+    m = re.findall(pattern, text, re.M)
+    if len(m) != 1:
+        raise AssertionError(f"size_classes: expected exactly one match for {what} ({pattern!r}), found {len(m)}")
+    return m[0]
+
+
+def _define(name, header):
+    return int(_one(r"^#define\s+" + name + r"\s+(\d+)\b", _src(header), name))
+
+
+def thresholds():
+    """dict of the named thresholds and of the literals of cons_class_of."""
+    t = dict(
+        big_stage_cap=_define("SNF_BIG_STAGE_CAP", "snf_wave_call.h"),
+        big_final_cap=_define("SNF_BIG_FINAL_CAP", "snf_stage_final.h"),
+        cons_small_l=_define("SNF_CONS_SMALL_L", "snf_stage_final.h"),
+        cons_large_l=_define("SNF_CONS_LARGE_L", "snf_stage_final.h"),
+        win_maxcap=_define("SNF_WIN_MAXCAP", "snf_stage_window.h"),
+        heavy_n=int(_one(r'int\s+heavy_n\s*=\s*env_int\(\s*"SNF_HEAVY_N"\s*,\s*(\d+)\s*\)', _src("snf_knobs.h"), "the heavy_n default")),
+        e1_batch=int(_one(r'int\s+e1_batch\s*=\s*env_int\(\s*"SNF_E1_BATCH"\s*,\s*(\d+)\s*\)', _src("snf_knobs.h"), "the e1_batch default")),
+    )
+    final = _src("snf_stage_final.h")
+    m = re.search(r"SNF_HD int cons_class_of\(int wave_path, int klen, int skip, int64_t L, int32_t n_others\) \{\n(.*?)\n\}", final, re.S)
+    if not m:
+        raise AssertionError("size_classes: cons_class_of is no longer found in snf_stage_final.h")
+    body = "\n".join(ln.split("//")[0] for ln in m.group(1).splitlines())
+    g = _one(r"if \(!wave_path \|\| klen > (\d+) \|\| klen < 1 \|\| skip < 1 \|\| L >= (\d+)\) return 0;", body, "the guard of cons_class_of")
+    s = _one(r"if \(npos <= (\d+) && n_others <= (\d+) && L <= SNF_CONS_SMALL_L && skip <= (\d+)\) return 1;", body, "the SMALL rule")
+    l = _one(r"if \(npos <= (\d+) && n_others <= (\d+) && L <= SNF_CONS_LARGE_L\) return 2;", body, "the LARGE rule")
+    r = _one(r"if \(npos <= (\d+) && n_others <= (\d+)\) return 4;", body, "the ROWS rule")
+    t.update(cons_klen_max=int(g[0]), cons_l_end=int(g[1]), small_npos=int(s[0]), small_others=int(s[1]), small_skip=int(s[2]),
+             large_npos=int(l[0]), large_others=int(l[1]), rows_npos=int(r[0]), rows_others=int(r[1]))
+    return t
+
+
+def cons_npos(L, klen, skip):
+    """snf_stage_final.h::cons_npos - sampled positions of a best read of L bases."""
+    m = L - klen
+    return 0 if m <= 0 else (m + skip - 1) // skip
+
+
+def cons_class(t, klen, skip, L, n_others):
+    """cons_class_of on the wave path, from the literals as read: 1 SMALL, 2 LARGE, 4 ROWS, 0 the thread kernels."""
+    if klen > t["cons_klen_max"] or klen < 1 or skip < 1 or L >= t["cons_l_end"]:
+        return 0
+    npos = cons_npos(L, klen, skip)
+    if npos <= t["small_npos"] and n_others <= t["small_others"] and L <= t["cons_small_l"] and skip <= t["small_skip"]:
+        return 1
+    if npos <= t["large_npos"] and n_others <= t["large_others"] and L <= t["cons_large_l"]:
+        return 2
+    if npos <= t["rows_npos"] and n_others <= t["rows_others"]:
+        return 4
+    return 0
+
+
+def around(*ts):
+    """t - 1, t, t + 1 for every threshold, ascending, without repeats."""
+    return sorted({x for t in ts for x in (t - 1, t, t + 1)})
+
+
+def ladder_sizes(with_window_cap=False):
+    """Lead counts of a cluster-size ladder: both sides of every size class of the cluster kernels (and 2 / 3, the smallest clusters
+    there are).  with_window_cap: also the largest window the front end takes (one ladder only: 3 000 leads more)."""
+    t = thresholds()
+    s = {2, 3} | set(around(GROUP, t["heavy_n"], HALF_WAVE, WAVE, TWO_WAVES, t["big_stage_cap"], WIN_MID, t["big_final_cap"]))
+    s |= {WAVE + 2, REF_METRICS, REF_METRICS + 1}
+    if with_window_cap:
+        s |= set(around(t["win_maxcap"]))
+    return sorted(s)
