@@ -1,7 +1,8 @@
 """The size thresholds at which the library changes kernel form, read from the sources by regular expression (the way
 tests/test_knobs.py reads the switches), and the ladders t - 1, t, t + 1 the directed cases of tests/cases.py and
 tests/test_size_classes.py are derived from.  A threshold that is no longer found is an error, not a default: a case that
-silently tests the middle of a class is what this module is there to prevent."""
+silently tests the middle of a class is what this module is there to prevent.  ed_thresholds(): the same for the edit-distance
+kernels and the merge kernel that calls them (tests/ed_edges.py, tests/test_edit_distance_edges.py)."""
 import os
 import re
 
@@ -53,6 +54,40 @@ def thresholds():
     t.update(cons_klen_max=int(g[0]), cons_l_end=int(g[1]), small_npos=int(s[0]), small_others=int(s[1]), small_skip=int(s[2]),
              large_npos=int(l[0]), large_others=int(l[1]), rows_npos=int(r[0]), rows_others=int(r[1]))
     return t
+
+
+def ed_thresholds():
+    """dict of the literals at which the edit-distance kernels (snf_myers.h / snf_myers.hip) and the merge kernel that calls them
+    (snf_combine.hip) change form.  Both copies of a rule that is written twice are reported; that they agree is for the tests to say."""
+    myers_h, myers, combine = _src("snf_myers.h"), _src("snf_myers.hip"), _src("snf_combine.hip")
+    fits = _one(r"return \(64 \+ bd\.dl \+ 2 \* bd\.kk\) / 64 \+ 2 <= (\d+) \|\| \(m \+ 63\) / 64 <= (\d+);", myers_h,
+                "the rule of ed_wave_band_fits")
+    wide = _one(r"wide = !\(\(64 \+ bd\.dl \+ 2 \* bd\.kk\) / 64 \+ 2 <= (\d+) \|\| \(m \+ 63\) / 64 <= (\d+)\);", myers,
+                "ed_batch's copy of the rule of ed_wave_band_fits")
+    ed_grid = _one(r"hipLaunchKernelGGL\(ed_wave, dim3\(\(unsigned\)\(v\.n < (\d+) \? v\.n : (\d+)\)\)", myers, "the grid cap of ed_wave")
+    cb_grid = _one(r"hipLaunchKernelGGL\(combine_problem_wave, dim3\(\(unsigned\)\(np < (\d+) \? np : (\d+)\)\)", combine,
+                   "the grid cap of combine_problem_wave")
+    for what, pair in (("the grid cap of ed_wave", ed_grid), ("the grid cap of combine_problem_wave", cb_grid)):
+        if pair[0] != pair[1]:
+            raise AssertionError(f"size_classes: {what} is written as two different numbers {pair}")
+    return dict(
+        thread_blocks=_define("SNF_ED_THREAD_BLOCKS", "snf_myers.hip"),
+        small_blocks=int(_one(r"const bool small = \(m \+ 63\) / 64 <= (\d+);", myers, "the `small` rule of ed_batch")),
+        band_blocks=int(fits[0]), band_pattern_blocks=int(fits[1]),
+        host_band_blocks=int(wide[0]), host_band_pattern_blocks=int(wide[1]),
+        ed_wave_grid=int(ed_grid[0]), combine_wave_grid=int(cb_grid[0]),
+        carry_min_len=int(_one(r"k_off\[p \+ 1\] = k_off\[p\] \+ \(maxlen > (\d+) \? maxlen \+ 8 : 8\);", combine,
+                               "the carry sizing rule of snf_combine_resolve_batch")),
+    )
+
+
+def ed_band_is_wide(t, m, n, k):
+    """not ed_wave_band_fits(m, n, k), from the literals as read (m <= n; k < 0: no cut-off): the pair takes the multi-pass form."""
+    dl = n - m
+    if k >= 0 and dl > k:
+        return False
+    kk = m if k < 0 else (k - dl) // 2
+    return not ((64 + dl + 2 * kk) // 64 + 2 <= t["band_blocks"] or (m + 63) // 64 <= t["band_pattern_blocks"])
 
 
 def cons_npos(L, klen, skip):
