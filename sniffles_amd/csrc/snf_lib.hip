@@ -1629,7 +1629,8 @@ void enqueue_output_head(snf_batch_impl* b) {
     FUSED(f2k_outscan, NS > 0 ? NS : 1);
     if ((v.out_mode & SNF_OUT_EXECUTE) && v.cfg.sort) {
       Scope _s(b, "f3_rank", 0);
-      hipLaunchKernelGGL(f3k_rank, dim3(grid < 1024u ? grid : 1024u), dim3(256), 0, b->cur, v, (int64_t)0);
+      const unsigned g3 = grid * (256u / F3_Q);      // a workgroup per F3_Q calls of the upper bound
+      hipLaunchKernelGGL(f3k_rank, dim3(g3 < 4096u ? g3 : 4096u), dim3(256), 0, b->cur, v, (int64_t)0);
       SNF_HIP(hipGetLastError());
     }
     { Scope _s(b, "f4_emit", 0);

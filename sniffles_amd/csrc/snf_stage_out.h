@@ -142,20 +142,68 @@ __global__ void __launch_bounds__(256) f2k_outscan(const View v, int64_t n) {
     }
   }
 }
-// one wave per kept call: the lanes stride over the keys of the call's task (contiguous, cache-resident) and the ballots are counted
+// f3_rank_body for F3_Q consecutive kept calls per workgroup.  The kept calls of a task are consecutive in q and the tasks follow each
+// other, so the calls a workgroup has to look at are ONE range: from the first slot of its first call's task to the end of its last
+// call's task.  That range passes through LDS in tiles of 256 words (pos ^ sign) << 32 | j - one 64-bit compare carries the order and
+// the tie rule (j < 2^31: o_dst is an int32).  Every wave of the workgroup holds the same 64 calls, one per lane, and counts the words
+// below its own in its quarter of the tile with broadcast reads: a read, a compare and an add-with-carry per word, no load from
+// global memory in the loop; the four partial ranks meet in LDS.  (64 calls, not 256, per workgroup: the kernel runs beside the ALT
+// kernels, and a pass keeps some 27 000 calls - a hundred workgroups would leave most CUs without a share of it.)  The words behind
+// the range are ~0, which no word is above, so a tile needs no bound test.  A workgroup whose calls all lie in one task (nearly all of
+// them) counts whatever it reads; one that straddles a task border tests every j against its own task's [qlo, qhi).  The number of
+// kept calls is known on the device only: the grid is the launch's upper bound, the loop block-uniform.
+#define F3_Q 64
+SNF_D uint64_t f3_word(int32_t key, int64_t j) { return ((uint64_t)((uint32_t)key ^ 0x80000000u) << 32) | (uint64_t)(uint32_t)j; }
 __global__ void __launch_bounds__(256) f3k_rank(const View v, int64_t n) {
+  constexpr int T = 256, P = T / F3_Q, U = 8;
+  __shared__ uint64_t tile[T];
+  __shared__ int64_t edge[4];      // qlo / qhi of the workgroup's first call, of its last one
+  __shared__ int part[P][F3_Q];
   const int64_t n_out = v.out_hdr->n_out;
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6, nw = ((int64_t)gridDim.x * 256) >> 6;
-  for (int64_t q = wave; q < n_out; q += nw) {
-    const int t = v.calls[v.o_src[q]].task_index;
-    const int64_t qlo = v.o_scan[v.t_call_off[t]], qhi = v.o_scan[v.t_call_off[t + 1]];
-    const int32_t key = v.o_key[q];
+  const int tid = threadIdx.x, qi = tid & (F3_Q - 1), p = tid / F3_Q;
+  for (int64_t q0 = (int64_t)blockIdx.x * F3_Q; q0 < n_out; q0 += (int64_t)gridDim.x * F3_Q) {
+    const int64_t q = q0 + qi;
+    const bool on = q < n_out;
+    int64_t qlo = 0, qhi = 0; uint64_t w = 0;
+    if (on) {
+      const int t = v.calls[v.o_src[q]].task_index;
+      qlo = v.o_scan[v.t_call_off[t]]; qhi = v.o_scan[v.t_call_off[t + 1]];
+      w = f3_word(v.o_key[q], q);
+    }
+    if (tid == 0) { edge[0] = qlo; edge[1] = qhi; }
+    if (p == 0 && on && (qi == F3_Q - 1 || q + 1 == n_out)) { edge[2] = qlo; edge[3] = qhi; }
+    __syncthreads();
+    const int64_t jlo = edge[0], jhi = edge[3];
+    const bool one_task = edge[2] == jlo;      // (block-uniform)
+    const uint64_t len = (uint64_t)(qhi - qlo);
+    const uint64_t* mine = tile + p * F3_Q;    // this wave's quarter of a tile
     int rank = 0;
-    for (int64_t j = qlo + lane; j < qhi; j += 64) { const int32_t kj = v.o_key[j]; rank += (kj < key || (kj == key && j < q)) ? 1 : 0; }
+    for (int64_t base = jlo; base < jhi; base += T) {
+      const int64_t j = base + tid;
+      tile[tid] = j < jhi ? f3_word(v.o_key[j], j) : ~0ull;
+      __syncthreads();
+      if (one_task) {
+        for (int u0 = 0; u0 < F3_Q; u0 += U) {
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) rank += __shfl_xor(rank, d, 64);
-    if (lane == 0) v.o_dst[q] = (int32_t)(qlo + rank);
+          for (int u = 0; u < U; u++) rank += mine[u0 + u] < w ? 1 : 0;
+        }
+      } else {
+        const int64_t b0 = base + p * F3_Q - qlo;
+        for (int u0 = 0; u0 < F3_Q; u0 += U) {
+#pragma unroll
+          for (int u = 0; u < U; u++) rank += (mine[u0 + u] < w && (uint64_t)(b0 + u0 + u) < len) ? 1 : 0;
+        }
+      }
+      __syncthreads();
+    }
+    part[p][qi] = rank;
+    __syncthreads();
+    if (p == 0 && on) {
+      int r = 0;
+#pragma unroll
+      for (int k = 0; k < P; k++) r += part[k][qi];
+      v.o_dst[q] = (int32_t)(qlo + r);
+    }
   }
 }
 typedef uint4 __attribute__((aligned(1))) out_u128_unaligned;

@@ -1,6 +1,6 @@
 // snf_wave_call.h - gfx950 wave-per-cluster implementations of sv.call_from / resolve_bnd (sv.py:497-639) and of
 // the lead aggregates Task.finalize_candidates needs (strand set, phase majorities; postprocessing.py:626-654).
-// One refined cluster (<= 64 leads) per wave, one lead per lane; sorts are rank sorts in registers, medians /
+// One refined cluster (<= 64 leads) per wave, one lead per lane; sorts are rank sorts over key rows in LDS, medians /
 // modes / trimmed variances are ballots and butterfly reductions over the sorted lanes.  Larger clusters use the
 // thread-per-cluster bodies (d2_call_body / e1_finalize_body), which are also what the host emulation runs.
 #pragma once
@@ -17,14 +17,57 @@ SNF_D int64_t wave_sum64(int64_t x) { return wave_last64(wave_incl_scan64(x, 0))
 SNF_D uint32_t wave_sum32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane(wave_incl_scan((int32_t)x, 0), 63); }
 SNF_D int wave_max32(int x) { return (int)__builtin_amdgcn_readlane((uint32_t)wave_incl_max(x), 63); }
 
-// ascending sort of the active lanes' values; returns the value at sorted position `lane` (lanes >= n: garbage)
-SNF_D int32_t wave_sort_i32(int32_t x, bool act, int n, int lane, int32_t* lds) {
-  const uint64_t key = act ? (((uint64_t)((uint32_t)x ^ 0x80000000u) << 8) | (uint32_t)lane) : ~0ull;
-  const int rank = wave_rank(key, n);
+// Ascending sorts of the active lanes' values, up to four sets of them in one pass over LDS.  A key is (value ^ sign) << 8 | lane, ~0 for
+// an inactive lane - distinct, and ties keep lane order; every set has a row of 64 keys (a lane that is not active in a set pads the
+// row with ~0: a rank loop unrolled by RANK_U runs to n rounded up and needs no bound per step), a row of sorted values and a row of
+// ranks.  A rank step is
+// one LDS read at an immediate offset, one 64-bit compare and one add-with-carry - wave_rank's step is two v_readlane, the compare, the
+// add and four scalar instructions - and the lanes that hold no lead work too: with n <= 16 lane L ranks element L & 15 of set L >> 4,
+// all four sets in one loop; with n <= 32 element L & 31 of set L >> 5, two sets per loop; above that a set per loop.  The lane that
+// holds a rank writes the value (it is in the key) to sorted[set][rank] and the rank to rk[set][element]; wave_sorted_at then
+// gives the value at sorted position `lane` of a set (lanes >= n: garbage).  Both rows stay readable until the next call: a caller
+// reads a set where it uses it and holds no register for it in between.  `ns` (wave-uniform): the sets in use, the first ns of the NS
+// rows.  All lanes must call it (two barriers).
+#define RANK_U 8
+#define RANK_ROW (SNF_WAVE + 2)      // keys per row + 2: the rows of the four quarters of a wave start in different banks
+// (nm: the row wave_lead_agg sums the NM ratios from, between two rank passes - it shares the key rows and their per-lane address)
+struct RankLds { union { uint64_t key[4][RANK_ROW]; double nm[SNF_WAVE]; }; int32_t sorted[4][SNF_WAVE]; uint8_t rk[4][SNF_WAVE]; };
+
+SNF_D uint64_t wave_sort_key(int32_t x, bool act, int lane) { return act ? (((uint64_t)((uint32_t)x ^ 0x80000000u) << 8) | (uint32_t)lane) : ~0ull; }
+template <int NS>
+SNF_D void wave_sort_sets(RankLds& L, int ns, int n, int lane, int32_t x0, bool a0, int32_t x1 = 0, bool a1 = false, int32_t x2 = 0, bool a2 = false,
+                          int32_t x3 = 0, bool a3 = false) {
+  static_assert(NS >= 1 && NS <= 4, "four rows");
+  L.key[0][lane] = wave_sort_key(x0, a0, lane);
+  if (NS > 1) L.key[1][lane] = wave_sort_key(x1, a1, lane);
+  if (NS > 2) L.key[2][lane] = wave_sort_key(x2, a2, lane);
+  if (NS > 3) L.key[3][lane] = wave_sort_key(x3, a3, lane);
   __syncthreads();
-  if (act) lds[rank] = x;
+  const int nr = (n + RANK_U - 1) & ~(RANK_U - 1);
+  const int shift = n <= 16 ? 4 : n <= 32 ? 5 : 6;      // a loop ranks 4 / 2 / 1 sets: lane L element L & (2^shift - 1) of set p + (L >> shift)
+  const int e = lane & ((1 << shift) - 1);
+  for (int p = 0; p < ns; p += SNF_WAVE >> shift) {
+    const int set = p + (lane >> shift);
+    const bool on = set < ns;
+    const uint64_t* row = &L.key[0][0] + (on ? set : 0) * RANK_ROW;
+    const uint64_t mine = row[e];
+    int r = 0;
+    for (int q = 0; q < nr; q += RANK_U) {
+#pragma unroll
+      for (int u = 0; u < RANK_U; u++) r += row[q + u] < mine ? 1 : 0;
+    }
+    if (on && mine != ~0ull) { L.sorted[set][r] = (int32_t)((uint32_t)(mine >> 8) ^ 0x80000000u); L.rk[set][e] = (uint8_t)r; }
+  }
   __syncthreads();
-  return lds[lane < n ? lane : 0];
+}
+SNF_D int32_t wave_sorted_at(const RankLds& L, int set, int n, int lane) { return L.sorted[set][lane < n ? lane : 0]; }
+
+// "a later active lead of the same read exists", from a set wave_sort_sets has just ranked by read (`cnt` active lanes): equal reads
+// are neighbours in the sorted row, in lane order - the key ends in the lane -, so it is the next entry that tells
+SNF_D bool wave_later_same(const RankLds& L, int set, bool act, int cnt, int lane, int32_t val) {
+  const int r = act ? (int)L.rk[set][lane] : 0;
+  const int32_t nx = L.sorted[set][r + 1 < cnt ? r + 1 : 0];
+  return act && r + 1 < cnt && nx == val;
 }
 
 // util.median_modes == center on lanes 0..n-1 holding a sorted array (util.py:49-58)
@@ -117,20 +160,15 @@ SNF_D void d2list_push(const View& v, int k, bool hand, int32_t r, int lane, int
 // reads (the last lead of a read wins, postprocessing.py:626-654), np.nanmean of the NM ratios (rescue_phasing) - over the
 // SELECTED leads of a cluster of n <= 64 leads, one lead per lane.  All lanes must call it.
 template <bool PHASE>
-SNF_D void wave_lead_agg(const snf_config_t& cfg, CallLds& lds, int lane, int n, bool sel, int strand, int hap, uint32_t rid, int32_t ps,
+SNF_D void wave_lead_agg(const snf_config_t& cfg, RankLds& rl, int lane, int n, bool sel, int strand, int hap, bool later, int32_t ps,
                          bool close, bool want_nm, double nm, CallX& x) {
   x.ag_valid = 1;
   x.ag_nstrands = (__ballot(sel && strand == 0) ? 1 : 0) + (__ballot(sel && strand != 0) ? 1 : 0);
   x.ag_close_edge = __builtin_popcountll(__ballot(sel && close));
   int hp_val = 0, hp_support = -1, hp_other = 0; int32_t ps_val = 0; int ps_support = -1, ps_other = 0;
   if (PHASE) {
-    // reads_phases = {read_id: (hap, ps)}: the last lead of a read wins
-    bool later = false;
-    for (int k = 0; k < n; k++) {
-      const uint32_t rk = (uint32_t)wave_bcast_i32((int32_t)rid, k);
-      const bool sk = wave_bcast_i32(sel ? 1 : 0, k) != 0;
-      if (k > lane && sk && rk == rid) later = true;
-    }
+    // reads_phases = {read_id: (hap, ps)}: the last lead of a read wins (`later`: a later selected lead of the lane's read exists;
+    // the caller has it from the read ids ranked along with its own sorts, wave_later_same)
     const bool contrib = sel && !later;
     int hc[3];
     for (int hh = 0; hh < 3; hh++) hc[hh] = __builtin_popcountll(__ballot(contrib && hap == hh));
@@ -138,12 +176,8 @@ SNF_D void wave_lead_agg(const snf_config_t& cfg, CallLds& lds, int lane, int n,
     for (int hh = 0; hh < 3; hh++) if (hh != hp_val) hp_other += hc[hh];
     const int np_ = __builtin_popcountll(__ballot(contrib));
     // phase sets of the contributing reads, sorted (non-contributors sort behind: rank sort on a wider key)
-    const uint64_t key = contrib ? (((uint64_t)((uint32_t)ps ^ 0x80000000u) << 8) | (uint32_t)lane) : ~0ull;
-    const int rank = wave_rank(key, n);
-    __syncthreads();
-    if (contrib) lds.buf[rank] = ps;
-    __syncthreads();
-    const int32_t s_ps = lds.buf[lane < np_ ? lane : 0];
+    wave_sort_sets<1>(rl, 1, n, lane, ps, contrib);
+    const int32_t s_ps = wave_sorted_at(rl, 0, np_, lane);
     const int32_t p_ps = __shfl_up(s_ps, 1, SNF_WAVE);
     const bool st = lane < np_ && (lane == 0 || p_ps != s_ps);
     const unsigned long long smask = __ballot(st);
@@ -164,18 +198,18 @@ SNF_D void wave_lead_agg(const snf_config_t& cfg, CallLds& lds, int lane, int n,
     // fewer than 8 values: left to right; otherwise eight accumulators r[q] over the positions q, q + 8, ... below
     // n - n % 8, combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail left to right.  NaN counts as 0 in the sum.
     const int cnt = __builtin_popcountll(__ballot(lane < n && nm == nm));
-    lds.nm[lane] = (lane < n && nm == nm) ? nm : 0.0;
+    rl.nm[lane] = (lane < n && nm == nm) ? nm : 0.0;
     __syncthreads();
     double res = 0.0;
-    if (n < 8) { for (int q = 0; q < n; q++) res += lds.nm[q]; }
+    if (n < 8) { for (int q = 0; q < n; q++) res += rl.nm[q]; }
     else {
       const int n8 = n - n % 8;
       double r = 0.0;
-      if (lane < 8) { r = lds.nm[lane]; for (int q = 8 + lane; q < n8; q += 8) r += lds.nm[q]; }
+      if (lane < 8) { r = rl.nm[lane]; for (int q = 8 + lane; q < n8; q += 8) r += rl.nm[q]; }
       double rq[8];
       for (int q = 0; q < 8; q++) rq[q] = __shfl(r, q, SNF_WAVE);
       res = ((rq[0] + rq[1]) + (rq[2] + rq[3])) + ((rq[4] + rq[5]) + (rq[6] + rq[7]));
-      for (int q = n8; q < n; q++) res += lds.nm[q];
+      for (int q = n8; q < n; q++) res += rl.nm[q];
     }
     x.ag_nm_mean = res / (double)cnt; x.ag_has_nm = 1;
     __syncthreads();
@@ -188,7 +222,7 @@ SNF_D void wave_lead_agg(const snf_config_t& cfg, CallLds& lds, int lane, int n,
 template <int MINW, bool PHASE>
 __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t n_unused) {
   IT_SCOPE(7)
-  __shared__ CallLds lds;
+  __shared__ RankLds rl;
   const int lane = threadIdx.x;
   const snf_config_t& cfg = v.cfg;
   // the refined clusters of this launch: all of them, or (View::d2_from_list) the ones the grouped kernels handed on
@@ -234,12 +268,18 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t
       v.F_sel[slot] = 1;
     }
     if (lane == 0) v.cdflag[r] = 0;
-    const int32_t s_svl = wave_sort_i32(svl, act, n, lane, lds.buf);
+    // the sorts of call_from in one rank pass (wave_sort_sets): svlen, read name, ref_start, and in the fourth row what the next step
+    // ranks by - the mate contig (resolve_bnd) or, for the phase tally, the read id.  The clusters the screen below drops have paid
+    // for the other rows: nothing when all four share a loop (n <= 16), little otherwise - and on the 30x genome the screen drops
+    // no cluster at all
+    const bool bnd = svtype == SNF_BND;
+    wave_sort_sets<4>(rl, (bnd || PHASE) ? 4 : 3, n, lane, svl, act, (int32_t)qn, act, rs, act, bnd ? mctg : (int32_t)rid, act && (bnd || PHASE));
+    const int32_t s_svl = wave_sorted_at(rl, 0, n, lane);
     const int64_t svlen = wave_center_sorted(s_svl, n, lane);
     const bool single = svtype == SNF_SINGLE_LEFT || svtype == SNF_SINGLE_RIGHT;
     if (!single && svtype != SNF_BND && iabs64(svlen) < cfg.minsvlen_screen) continue;
     // distinct read names, sorted (kept in w1 for d3_rnames)
-    const int32_t s_qn = wave_sort_i32((int32_t)qn, act, n, lane, lds.buf);
+    const int32_t s_qn = wave_sorted_at(rl, 1, n, lane);
     const int32_t p_qn = __shfl_up(s_qn, 1, SNF_WAVE);
     const bool qfirst = act && (lane == 0 || p_qn != s_qn);
     const unsigned long long qmask = __ballot(qfirst);
@@ -263,7 +303,7 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t
       }
       support_long = wave_sum32((uint32_t)cl); support += wave_sum32((uint32_t)cu);
     }
-    const int32_t s_rs = wave_sort_i32(rs, act, n, lane, lds.buf);
+    const int32_t s_rs = wave_sorted_at(rl, 2, n, lane);
     const int64_t ref_start = wave_center_sorted(s_rs, n, lane);
     const double stdev_pos = wave_stdev_trim_sorted(s_rs, n, lane);
     double stdev_len = NAN; bool precise;
@@ -296,16 +336,17 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t
     cc.support = (int32_t)support; cc.support_long = -1; cc.support_sa = -1;
     cc.qual = (int32_t)((double)msum / (double)n); cc.precise = precise; cc.fwd = (int32_t)fwd; cc.rev = (int32_t)(n - fwd);
     cc.qc = 1; cc.filter = SNF_F_PASS;
-    cc.nm = cfg.qc_nm_measure ? nmsum / (double)n : -1.0;
-    cc.stdev_pos = stdev_pos; cc.stdev_len = stdev_len;
-    cc.sa_count = (int32_t)sa; cc.sa_frac = (double)sa / (double)n_all; cc.n_leads = n;
-    cc.mate_contig = -1; cc.gt_hp = -1; cc.gt_ps = -1; cc.vaf = NAN; cc.alt_len = -1;
+    // (the record's doubles go from their registers straight into the stored record below: as fields of `cc` on top of its memset
+    // they end up as stack slots)
+    const double c_nm = cfg.qc_nm_measure ? nmsum / (double)n : -1.0;
+    cc.sa_count = (int32_t)sa; const double c_sa_frac = (double)sa / (double)n_all; cc.n_leads = n;
+    cc.mate_contig = -1; cc.gt_hp = -1; cc.gt_ps = -1; cc.alt_len = -1;
     cc.cluster_start = v.seed_start[h]; cc.cluster_end = v.c_end[h];
     cc.cluster_seed_index = v.prefilter ? -1 : v.seed_bin[h] - v.grp_first_bin[g];
     int64_t rn_len = support;
     bool sel_final = act;     // the leads the call keeps (resolve_bnd narrows them)
     if (svtype == SNF_BND) {  // resolve_bnd (sv.py:625-639)
-      const int32_t s_mc = wave_sort_i32(mctg, act, n, lane, lds.buf);
+      const int32_t s_mc = wave_sorted_at(rl, 3, n, lane);
       const int32_t p_mc = __shfl_up(s_mc, 1, SNF_WAVE);
       const bool st = act && (lane == 0 || p_mc != s_mc);
       const unsigned long long smask = __ballot(st);
@@ -320,10 +361,10 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t
       const unsigned long long selmask = __ballot(sel);
       const int ns = __builtin_popcountll(selmask);
       const int64_t nfirst = __builtin_popcountll(__ballot(sel && bfirst)), nrev = __builtin_popcountll(__ballot(sel && brev));
-      // selected values packed to the front by sorting with +inf for the rest
-      const int32_t s_mp = wave_sort_i32(sel ? mpos : INT32_MAX, act, n, lane, lds.buf);
+      // selected values packed to the front by sorting with +inf for the rest; third row: the selected leads by read id (phase tally)
+      wave_sort_sets<3>(rl, PHASE ? 3 : 2, n, lane, sel ? mpos : INT32_MAX, act, sel ? (int32_t)qn : INT32_MAX, act, (int32_t)rid, PHASE && sel);
+      const int32_t s_mp = wave_sorted_at(rl, 0, n, lane), s_q2 = wave_sorted_at(rl, 1, n, lane);
       const int64_t mate_pos = wave_center_sorted(s_mp, ns, lane);
-      const int32_t s_q2 = wave_sort_i32(sel ? (int32_t)qn : INT32_MAX, act, n, lane, lds.buf);
       const int32_t p_q2 = __shfl_up(s_q2, 1, SNF_WAVE);
       const bool qf2 = lane < ns && (lane == 0 || p_q2 != s_q2);
       const unsigned long long qm2 = __ballot(qf2);
@@ -367,9 +408,15 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t
     CallX x; x.rc = (int32_t)r; x.cluster = c; x.flo = flo; x.fn = n; x.best = best_slot; x.n_others = n_others;
     x.do_cons = (best_slot >= 0 && n_others >= cfg.consensus_min_reads && !cfg.no_consensus) ? 1 : 0; x.cons_id = -1; x.alt_off = 0;
     x.rn_nq = (int32_t)nq; x._pad = 0;
-    wave_lead_agg<PHASE>(cfg, lds, lane, n, sel_final, strand, hap, rid, ps, close, want_nm, nm, x);
+    if (lane == 0) {      // (before the aggregates: they need the registers the record holds)
+      snf_call_t& o = v.cand[r];
+      o = cc;
+      o.nm = c_nm; o.stdev_pos = stdev_pos; o.stdev_len = stdev_len; o.sa_frac = c_sa_frac; o.vaf = NAN;
+    }
+    // a later selected lead of the lane's read: the read ids lie ranked in the last row of the last pass (cc.n_leads selected leads)
+    const bool later = PHASE && wave_later_same(rl, bnd ? 2 : 3, sel_final, cc.n_leads, lane, (int32_t)rid);
+    wave_lead_agg<PHASE>(cfg, rl, lane, n, sel_final, strand, hap, later, ps, close, want_nm, nm, x);
     if (lane == 0) {
-      v.cand[r] = cc;
       v.candx[r] = x;
       v.cdflag[r] = 1;
     }
