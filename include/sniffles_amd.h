@@ -538,6 +538,45 @@ int snf_combine_resolve_batch(const snf_config_t* cfg, int device, const snf_com
 int snf_combine_last_stats(int device, double* kernel_ms, int64_t* stats4);
 
 /*
+ * Multi-sample combine, population annotation (--combine-population): PopulationSNF.get_population_AF
+ * (src/sniffles/snfp.py:131-155) over PopulationVariant.match (snfp.py:91-107) for ALL merged calls of a merge in one
+ * launch.  The variant lists of the population file - one per (contig, block, SV type), file order - are given as a CSR;
+ * a query is a merged call (pos, svlen, ALT) and the list it searches (-1: its contig / block / type is not in the file).
+ * For every variant of the list, in order:  dist = |v.pos - q.pos| + ||v.svlen| - |q.svlen||,
+ * minlen = min(|v.svlen|, |q.svlen|); rejected if dist > combine_match * sqrt(minlen) or dist > combine_match_max (fp64);
+ * in a list with list_is_ins and combine_pctseq != 0 also if (v.svlen - d) / v.svlen <= combine_pctseq with d the global
+ * unit-cost edit distance of the two ALTs (such a list must hold v.svlen > 0 only: the call fails otherwise).  The answer is
+ * the accepted variant of smallest dist, the first in list order among equals: out_best = its index over all variants
+ * (-1: none), out_dist = its dist.  The survivors of the positional gate are aligned in ascending (dist, index) order and the
+ * search ends at the first accepted one, so most alignments are never run.  Staged through a persistent per-device arena
+ * like the other combine entry points; SNF_COMBINE_THREAD selects the thread-per-query form.
+ */
+typedef struct snf_popmatch {
+  int64_t n_lists;
+  const int64_t* list_off;     /* n_lists + 1: list l = variants [list_off[l], list_off[l+1]) */
+  const uint8_t* list_is_ins;  /* n_lists: svtype == "INS" */
+  int64_t n_variants;          /* == list_off[n_lists] */
+  const int32_t* v_pos;
+  const int32_t* v_svlen;      /* the stored integer (not len(alt)) */
+  const int64_t* v_alt_off;    /* n_variants + 1 offsets into v_alt_pool */
+  const uint8_t* v_alt_pool;
+  int64_t n_queries;
+  const int32_t* q_pos;
+  const int32_t* q_svlen;
+  const int32_t* q_list;       /* list index, -1: no list */
+  const int64_t* q_alt_off;    /* n_queries + 1 offsets into q_alt_pool */
+  const uint8_t* q_alt_pool;
+  int32_t* out_best;           /* n_queries */
+  int32_t* out_dist;           /* n_queries */
+} snf_popmatch_t;
+
+int snf_population_match_batch(const snf_config_t* cfg, int device, const snf_popmatch_t* in);
+/* measurement: kernel time (HIP events) of the last snf_population_match_batch on `device` and what it aligned - stats4 as
+ * snf_combine_last_stats: [0] alignments, [1] bytes of the aligned strings, [2] cells of their full DP matrices, [3] bytes
+ * staged host -> HBM */
+int snf_population_last_stats(int device, double* kernel_ms, int64_t* stats4);
+
+/*
  * Multi-sample combine, second half: SVGroup.call (src/sniffles/sv.py:320-481) and the keep / flush bookkeeping of
  * CombineTask.execute (src/sniffles/parallel.py:536-572) for ALL groups of a merge at once, over a columnar candidate
  * table - no per-object work.  The caller gives every candidate as one numeric record, the membership

@@ -142,6 +142,17 @@ class snf_combine_problem_t(C.Structure):
     ]
 
 
+class snf_popmatch_t(C.Structure):
+    _fields_ = [
+        ("n_lists", i64), ("list_off", C.POINTER(C.c_int64)), ("list_is_ins", u8p),
+        ("n_variants", i64), ("v_pos", C.POINTER(C.c_int32)), ("v_svlen", C.POINTER(C.c_int32)),
+        ("v_alt_off", C.POINTER(C.c_int64)), ("v_alt_pool", u8p),
+        ("n_queries", i64), ("q_pos", C.POINTER(C.c_int32)), ("q_svlen", C.POINTER(C.c_int32)), ("q_list", C.POINTER(C.c_int32)),
+        ("q_alt_off", C.POINTER(C.c_int64)), ("q_alt_pool", u8p),
+        ("out_best", C.POINTER(C.c_int32)), ("out_dist", C.POINTER(C.c_int32)),
+    ]
+
+
 def combine_problem(svtype_code: int, cands: dict, groups: dict, n_sample_ids: int, keep: list, windows=None):
     """Pack one resolve_block_groups call.  `cands`: pos, svlen, support, sample_id, mate_contig, mate_ref_start
     (int lists) and alts (list of bytes); `groups`: pos_mean, len_mean, mate_mean, size, mate_contig, alts, samples

@@ -395,6 +395,30 @@ def _text_threads(n_records: int) -> int:
     return max(1, min(8, (os.cpu_count() or 2) // 2, n_records // 2000))
 
 
+def _population_columns(tasks, config, device, gout, em, g_task, g_typ, member, aoff, apool):
+    """`(POPULATION_AF, POPULATION_SIZE)` of the emitted groups `em` - float64 (NaN: nothing matched) and int64 - or None without
+    `config.combine_population`.  A query is the finished call of a group: `gout["pos"]`, `gout["svlen"]`, its SV type, its task's
+    contig and, for an insertion, the chosen ALT (a slice of the candidate pool)."""
+    from . import snfp
+    pop = snfp.population_of(config)
+    if pop is None:
+        return None
+    if len(em) == 0:
+        return np.zeros(0, np.float64), np.zeros(0, np.int64)
+    t = pop.table()
+    contig_no = np.asarray([t["contigs"].get(task.contig, -1) for task in tasks], np.int64)[g_task[em]]
+    type_no = np.asarray([t["types"].get(name, -1) for name in sv.TYPES], np.int64)[g_typ[em]]
+    pos = gout["pos"][em]
+    chosen_alt = member[gout["alt_member"][em]].astype(np.int64)
+    length = np.where(g_typ[em] == sv.TYPES.index("INS"), aoff[chosen_alt + 1] - aoff[chosen_alt], 0)
+    q_off = np.concatenate(([0], np.cumsum(length))).astype(np.int64)
+    pool = apool if isinstance(apool, np.ndarray) else np.frombuffer(apool, np.uint8)
+    q_pool = pool[np.repeat(aoff[chosen_alt] - q_off[:-1], length) + np.arange(int(q_off[-1]), dtype=np.int64)]
+    af, size = pop.get_population_AF_batch(dict(list=pop.lists_of(contig_no, pos, type_no), pos=pos, svlen=gout["svlen"][em],
+                                                alt_off=q_off, alt_pool=q_pool), config=config, device=device)
+    return np.ascontiguousarray(af, np.float64), np.ascontiguousarray(size, np.int64)
+
+
 def _record_timing(timings, marks, **counts) -> None:
     """Phases of one `_execute_many`: into `last_timing`, or (a chunk of a merge) appended to `timings` for the caller to add up."""
     d = {name: t1 - t0 for (_, t0), (name, t1) in zip(marks[:-1], marks[1:])}
@@ -598,11 +622,14 @@ def _execute_many(tasks: list, samples_snf: dict, text_writer=None, timings: lis
                         em_typ=np.ascontiguousarray(g_typ[em], np.int32), alt_off=np.ascontiguousarray(aoff, np.int64), alt_pool=apool,
                         threads=_text_threads(len(em)))
     gc_covx = None if covx is None else {k: v for k, v in covx.items() if k not in ("ids", "alt_ascii")}
+    # --combine-population (sv.py:475-479): every emitted group is one query of ONE launch, all tasks together
+    pop_cols = _population_columns(tasks, config, device, gout, em, g_task, g_typ, member, aoff, apool)
+    mark("population_gpu")
     calls = fast.group_calls(sv.SVCall, sv.ForwardDifferenceWelford, objs, np.ascontiguousarray(gout), np.ascontiguousarray(em, np.int64),
                              group_off, member, chosen, np.ascontiguousarray(sv_ids, np.int64), np.ascontiguousarray(task_ids, np.int64),
                              sample_ids, spos, block_cov, ev_off, ev_block, np.ascontiguousarray(ev_bin),
                              int(config.combine_null_min_coverage), str(config.id_prefix), len(config.snf_input_info) == 1,
-                             np.ascontiguousarray(rec["sample"], np.int32), topt, gc_covx)
+                             np.ascontiguousarray(rec["sample"], np.int32), topt, gc_covx, pop_cols)
     if topt is not None:
         text, line_off, line_pos = calls
         line_off, line_pos = np.frombuffer(line_off, np.int64), np.frombuffer(line_pos, np.int64)

@@ -52,6 +52,8 @@ _DEFAULTS = dict(
     dev_minreads_extra=5, dev_maxsvlen_extra=10000, dev_inline_sa_support_max=0.80,
     dev_min_close_edge_dist=500, dev_min_read_close_edge_prop=0.75, dev_seq_cache_maxlen=50000,
     dev_emit_sv_lengths=False, dev_trace_read=False, dev_locasm_do=False, dev_dump_clusters=False,
+    # population SNF of a merge (config.py:367-368, 427-428; sniffles:272-280)
+    dev_population_snf=None, dev_population_min_gt=0.75,
 )
 
 

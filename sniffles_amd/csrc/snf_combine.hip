@@ -49,6 +49,19 @@ struct LessSupportDesc {
   SNF_HD bool operator()(int32_t a, int32_t b) const { return support[a] != support[b] ? support[a] > support[b] : a < b; }
 };
 
+// The cut-off of an alignment whose distance d is only asked "is ((gl - d) / gl) > pctseq ?" (SVGroup.align_call with gl = the
+// group's len_mean, PopulationVariant.match with gl = the variant's svlen): the largest d that still satisfies it, found with the
+// predicate itself - exact at the rounding edges -, at most `dcap` (no distance exceeds the longer string); -1: not even identical
+// strings would be accepted.
+SNF_HD long long align_cutoff(double gl, double pctseq, long long dcap) {
+  long long d0 = (long long)floor(gl * (1.0 - pctseq));
+  if (d0 > dcap) d0 = dcap;
+  if (d0 < 0) d0 = 0;
+  while (d0 < dcap && ((gl - (double)(d0 + 1)) / gl) > pctseq) d0++;
+  while (d0 >= 0 && !(((gl - (double)d0) / gl) > pctseq)) d0--;
+  return d0;
+}
+
 // One problem (a flush window, or a whole chain of them) - the thread form (WAVE == false: emulation build and
 // SNF_COMBINE_THREAD=1) and the gfx950 wave form share this body.  WAVE: one wave per problem, lane 0 ("lead") runs the
 // sequential greedy assignment and, whenever a (group, candidate) pair passes the distance gates, all 64 lanes evaluate
@@ -133,15 +146,8 @@ SNF_HD void combine_run(int64_t p, const CombineView& v) {
         // still satisfies it matter, so the alignment is banded with that cut-off (Ukkonen) and answers -1 beyond it
         long long kmax = -1;
         if (need && lead) {
-          const double gl = glen[g];
-          long long d0 = (long long)floor(gl * (1.0 - cfg.combine_pctseq));
-          const long long dcap = la > lb ? la : lb;          // no distance exceeds the longer string
-          if (d0 > dcap) d0 = dcap;
-          if (d0 < 0) d0 = 0;
-          while (d0 < dcap && ((gl - (double)(d0 + 1)) / gl) > cfg.combine_pctseq) d0++;
-          while (d0 >= 0 && !(((gl - (double)d0) / gl) > cfg.combine_pctseq)) d0--;
-          if (d0 < 0) need = 0;                               // not even identical strings would be accepted
-          kmax = d0;
+          kmax = align_cutoff(glen[g], cfg.combine_pctseq, la > lb ? la : lb);
+          if (kmax < 0) need = 0;                             // not even identical strings would be accepted
         }
         int64_t d = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -207,17 +213,128 @@ __global__ void __launch_bounds__(64) combine_problem_wave(const CombineView v, 
   for (int64_t p = blockIdx.x; p < np; p += gridDim.x) combine_run<true>(p, v);
 }
 
+// ---- population annotation: PopulationSNF.get_population_AF (snfp.py:131-155) over PopulationVariant.match (snfp.py:91-107)
+// for all merged calls of a merge.  A query is a call with the variant list of its (contig, block, SV type); the answer is the
+// variant of smallest dist = |pos - pos| + ||svlen| - |svlen|| that passes the positional gate and, for insertions, the sequence
+// gate - the first in list order among equals.  The gate costs a handful of integer operations and one sqrt, the sequence gate an
+// alignment: the survivors of the gate are tried in ascending (dist, list index) order and the search stops at the first one the
+// sequence gate accepts - the reference's answer with the fewest alignments.
+struct PopView {
+  double pctseq; int32_t combine_match, combine_match_max;
+  int64_t n_queries;
+  const int64_t* list_off; const uint8_t* list_is_ins;                                           // per list
+  const int32_t *v_pos, *v_svlen; const int64_t* v_alt_off; const uint8_t* v_alt_pool;           // per variant (list order)
+  const int32_t *q_pos, *q_svlen, *q_list; const int64_t* q_alt_off; const uint8_t* q_alt_pool;  // per query
+  const int64_t* k_off; int8_t* carry;             // Myers carry row per query (multi-pass wave form)
+  const int64_t* e_off; uint64_t* ed_scratch;      // serial Myers block states per query (thread form)
+  int32_t *out_best, *out_dist;
+  unsigned long long* stats;                       // as CombineView::stats
+};
+
+// One query - thread form (WAVE == false) and wave form share the body.  WAVE: the lanes stride over the list for the gate, a
+// wave-min over (dist, list index) picks the next survivor (every lane ends up with the same key, so everything behind it is
+// wave-uniform) and all 64 lanes align it together, exactly as combine_run<true> does.
+template <bool WAVE>
+SNF_HD void popmatch_run(int64_t q, const PopView& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const int lane = WAVE ? (int)(threadIdx.x & 63) : 0;
+#else
+  const int lane = 0;
+#endif
+  const int64_t step = WAVE ? 64 : 1;
+  const int64_t none = INT64_MAX;
+  const int32_t li = v.q_list[q];
+  int32_t best = -1, best_dist = 0;
+  if (li >= 0) {
+    const int64_t l0 = v.list_off[li], n = v.list_off[li + 1] - l0;
+    const int64_t cpos = v.q_pos[q], cl = v.q_svlen[q], clen = cl < 0 ? -cl : cl;
+    const bool seq = v.list_is_ins[li] != 0 && v.pctseq != 0.0;
+    const uint8_t* qa = v.q_alt_pool + v.q_alt_off[q];
+    const int64_t lq = v.q_alt_off[q + 1] - v.q_alt_off[q];
+    int8_t* carry = v.carry + v.k_off[q];
+    uint64_t* ed_scr = v.ed_scratch + v.e_off[q];
+    (void)carry; (void)ed_scr;
+    int64_t found = none;  // key of the accepted survivor, unpacked behind the loop (the one value that leaves it)
+    int64_t last = -1;     // (dist << 32 | list index) of the survivor tried last: keys are distinct, the next one is the smallest above it
+    for (;;) {
+      int64_t key = none;
+      for (int64_t i = lane; i < n; i += step) {
+        const int64_t vl = v.v_svlen[l0 + i], vlen = vl < 0 ? -vl : vl;
+        const int64_t dp = (int64_t)v.v_pos[l0 + i] - cpos, dl = vlen - clen;
+        const int64_t dist = (dp < 0 ? -dp : dp) + (dl < 0 ? -dl : dl);
+        const double minlen = (double)(vlen < clen ? vlen : clen);
+        if ((double)dist <= (double)v.combine_match * sqrt(minlen) && (double)dist <= (double)v.combine_match_max) {   // (dist < 2^31 from here)
+          const int64_t k = dist << 32 | i;
+          if (k > last && k < key) key = k;
+        }
+      }
+#if defined(__HIP_DEVICE_COMPILE__)
+      if (WAVE) {
+        for (int d = 32; d >= 1; d >>= 1) { const long long o = __shfl_xor((long long)key, d, 64); if (o < key) key = o; }
+      }
+#endif
+      if (key == none) break;          // no survivor left
+      last = key;
+      const int64_t gi = l0 + (key & 0xffffffffll), dist = key >> 32;
+      bool ok = true;
+      if (seq) {                       // PopulationVariant.match: (svlen - d) / svlen <= combine_pctseq rejects
+        ok = false;
+        const double gl = (double)v.v_svlen[gi];
+        const uint8_t* pa = v.v_alt_pool + v.v_alt_off[gi];
+        const int64_t la = v.v_alt_off[gi + 1] - v.v_alt_off[gi];
+        const long long kmax = align_cutoff(gl, v.pctseq, la > lq ? la : lq);
+        if (kmax >= 0) {
+          int64_t d = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+          if (WAVE) {
+            if (ed_wave_band_fits(la, lq, (int64_t)kmax)) d = ed_wave_pair_k_any(pa, la, qa, lq, (int64_t)kmax);
+            else { d = ed_wave_pair(pa, la, qa, lq, carry); if (d > kmax) d = -1; }
+          } else
+#endif
+          d = ed_serial_k(pa, la, qa, lq, (int64_t)kmax, ed_scr);
+          if (lane == 0) {
+            const int sx = (int)(q & 63);
+            atomic_add_u64(&v.stats[(0 * 64 + sx) * 16], 1ull);
+            atomic_add_u64(&v.stats[(1 * 64 + sx) * 16], (unsigned long long)(la + lq));
+            atomic_add_u64(&v.stats[(2 * 64 + sx) * 16], (unsigned long long)la * (unsigned long long)lq);
+          }
+          ok = d >= 0 && ((gl - (double)d) / gl) > v.pctseq;
+        }
+      }
+      if (ok) { found = key; break; }
+    }
+    if (found != none) { best = (int32_t)(l0 + (found & 0xffffffffll)); best_dist = (int32_t)(found >> 32); }
+  }
+  if (lane == 0) { v.out_best[q] = best; v.out_dist[q] = best_dist; }
+}
+
+SNF_HD void popmatch_body(int64_t q, const PopView& v) { popmatch_run<false>(q, v); }
+
+__global__ void __launch_bounds__(64) popmatch_wave(const PopView v, int64_t nq) {
+  for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) popmatch_run<true>(q, v);
+}
+
 }  // namespace snf
 using namespace snf;
 SNF_KERNEL(combine_problem, CombineView)
 SNF_KERNEL(group_call, GroupCallView)
+SNF_KERNEL(popmatch, PopView)
 
 namespace {
 DevArena g_combine_arenas[SNF_MAX_DEVICES];
 DevArena g_groupcall_arenas[SNF_MAX_DEVICES];
+DevArena g_popmatch_arenas[SNF_MAX_DEVICES];
 
 // an array of the call inside the arena: where it lives and (inputs) the host vector that fills it
 struct Slot { size_t off, bytes; const void* src; };
+
+// scratch rows of problem / query p whose longest string has `maxlen` bytes (the one rule of both entry points below) - per-column
+// carry bytes: only the multi-pass wave form needs them (a band of more than 63 blocks: strings > 4 kb that differ a lot); block
+// states of the serial form: emulation / SNF_COMBINE_THREAD
+inline void scratch_rows(std::vector<int64_t>& k_off, std::vector<int64_t>& e_off, int64_t p, int64_t maxlen) {
+  k_off[p + 1] = k_off[p] + (maxlen > 4000 ? maxlen + 8 : 8);
+  e_off[p + 1] = e_off[p] + ed_serial_scratch_words(maxlen);
+}
 }  // namespace
 
 extern "C" int snf_combine_resolve_batch(const snf_config_t* cfg, int device, const snf_combine_problem_t* P, int64_t np) {
@@ -235,10 +352,7 @@ extern "C" int snf_combine_resolve_batch(const snf_config_t* cfg, int device, co
     int64_t maxlen = 1;
     for (int i = 0; i < P[p].n_cands; i++) { int64_t l = P[p].alt_off[i + 1] - P[p].alt_off[i]; if (l > maxlen) maxlen = l; }
     for (int g = 0; g < P[p].n_groups; g++) { int64_t l = P[p].g_alt_off[g + 1] - P[p].g_alt_off[g]; if (l > maxlen) maxlen = l; }
-    // per-column carry bytes: only the multi-pass wave form needs them (a band of more than 63 blocks: strings > 4 kb
-    // that differ a lot); block states of the serial form: emulation / SNF_COMBINE_THREAD
-    k_off[p + 1] = k_off[p] + (maxlen > 4000 ? maxlen + 8 : 8);
-    e_off[p + 1] = e_off[p] + ed_serial_scratch_words(maxlen);
+    scratch_rows(k_off, e_off, p, maxlen);
   }
   // flush windows per problem (a plain problem = one window that flushes nothing)
   std::vector<int64_t> wn_off(np + 1, 0);
@@ -374,6 +488,113 @@ extern "C" int snf_combine_resolve_batch(const snf_config_t* cfg, int device, co
 extern "C" int snf_combine_last_stats(int device, double* kernel_ms, int64_t* stats4) {
   if (device < 0 || device >= SNF_MAX_DEVICES || !kernel_ms || !stats4) return 1;
   DevArena& A = g_combine_arenas[device];
+  std::lock_guard<std::mutex> hold(A.mu);
+  *kernel_ms = A.last_kernel_ms;
+  for (int k = 0; k < 4; k++) stats4[k] = A.last_stats[k];
+  return 0;
+}
+
+// PopulationSNF.get_population_AF for all merged calls of a merge (include/sniffles_amd.h): variant lists as a CSR, one query per
+// call, one launch.  The caller's arrays go straight into the staging mirror; only the scratch offsets are computed here.
+extern "C" int snf_population_match_batch(const snf_config_t* cfg, int device, const snf_popmatch_t* in) {
+  if (!cfg || !in) return 1;
+  if (device < 0 || device >= SNF_MAX_DEVICES) return 1;
+  const int64_t nq = in->n_queries, nl = in->n_lists, nv = in->n_variants;
+  if (nq <= 0) return nq < 0;
+  if (nl < 0 || nv < 0 || !in->list_off || !in->q_pos || !in->q_svlen || !in->q_list || !in->q_alt_off || !in->out_best || !in->out_dist) return 1;
+  if (nl > 0 && !in->list_is_ins) return 1;
+  if (nv > 0 && (!in->v_pos || !in->v_svlen || !in->v_alt_off)) return 1;
+  if (in->list_off[0] != 0 || in->list_off[nl] != nv || nv >= ((int64_t)1 << 31)) return 1;
+  const bool seq = cfg->combine_pctseq != 0.0;
+  const int64_t v0 = nv > 0 ? in->v_alt_off[0] : 0, q0 = in->q_alt_off[0];
+  const int64_t v_bytes = nv > 0 ? in->v_alt_off[nv] - v0 : 0, q_bytes = in->q_alt_off[nq] - q0;
+  if (v_bytes < 0 || q_bytes < 0 || (v_bytes > 0 && !in->v_alt_pool) || (q_bytes > 0 && !in->q_alt_pool)) return 1;
+  std::vector<int64_t> list_maxlen((size_t)nl + 1, 0);     // longest ALT of a list that is aligned at all
+  for (int64_t l = 0; l < nl; l++) {
+    if (in->list_off[l + 1] < in->list_off[l]) return 1;
+    for (int64_t i = in->list_off[l]; i < in->list_off[l + 1]; i++) {
+      const int64_t len = in->v_alt_off[i + 1] - in->v_alt_off[i];
+      if (len < 0) return 1;
+      if (in->list_is_ins[l] && seq) {
+        if (in->v_svlen[i] <= 0) return 1;                 // the reference divides by svlen: PopulationSNF.table() refuses the file
+        if (len > list_maxlen[l]) list_maxlen[l] = len;
+      }
+    }
+  }
+  std::vector<int64_t> k_off((size_t)nq + 1, 0), e_off((size_t)nq + 1, 0);
+  for (int64_t q = 0; q < nq; q++) {
+    const int64_t len = in->q_alt_off[q + 1] - in->q_alt_off[q];
+    if (len < 0 || in->q_list[q] < -1 || in->q_list[q] >= nl) return 1;
+    int64_t maxlen = 1;
+    if (in->q_list[q] >= 0 && in->list_is_ins[in->q_list[q]] && seq) {
+      maxlen = list_maxlen[in->q_list[q]] > len ? list_maxlen[in->q_list[q]] : len;
+      if (maxlen < 1) maxlen = 1;
+    }
+    scratch_rows(k_off, e_off, q, maxlen);
+  }
+  const bool thread_form = CombineKnobs().thread_form;
+  ArenaLayout L;
+  const size_t o_loff = L.add<int64_t>((size_t)nl + 1), o_lins = L.add<uint8_t>((size_t)nl);
+  const size_t o_vpos = L.add<int32_t>((size_t)nv), o_vlen = L.add<int32_t>((size_t)nv), o_vaoff = L.add<int64_t>((size_t)nv + 1);
+  const size_t o_qpos = L.add<int32_t>((size_t)nq), o_qlen = L.add<int32_t>((size_t)nq), o_qlist = L.add<int32_t>((size_t)nq);
+  const size_t o_qaoff = L.add<int64_t>((size_t)nq + 1), o_koff = L.add<int64_t>((size_t)nq + 1), o_eoff = L.add<int64_t>((size_t)nq + 1);
+  const size_t o_valt = L.add<uint8_t>((size_t)v_bytes + 32), o_qalt = L.add<uint8_t>((size_t)q_bytes + 32);   // (Myers reads 8-byte words)
+  const size_t in_end = (L.at + 255) & ~(size_t)255;
+  const size_t o_carry = L.add<int8_t>((size_t)k_off[nq] + 16);
+  const size_t o_edscr = L.add<uint64_t>(thread_form ? (size_t)e_off[nq] + 16 : 16);
+  const size_t o_best = L.add<int32_t>((size_t)nq), o_dist = L.add<int32_t>((size_t)nq);
+  const size_t o_stats = L.add<unsigned long long>(3 * 64 * 16);
+  DevArena& A = g_popmatch_arenas[device];
+  std::lock_guard<std::mutex> hold(A.mu);
+  if (!A.ensure(device, L.at)) return 1;
+  uint8_t *h = A.h, *d = A.d;
+  memcpy(h + o_loff, in->list_off, ((size_t)nl + 1) * 8);
+  if (nl) memcpy(h + o_lins, in->list_is_ins, (size_t)nl);
+  if (nv) { memcpy(h + o_vpos, in->v_pos, (size_t)nv * 4); memcpy(h + o_vlen, in->v_svlen, (size_t)nv * 4); }
+  { int64_t* w = (int64_t*)(h + o_vaoff); w[0] = 0; for (int64_t i = 0; i < nv; i++) w[i + 1] = in->v_alt_off[i + 1] - v0; }
+  memcpy(h + o_qpos, in->q_pos, (size_t)nq * 4); memcpy(h + o_qlen, in->q_svlen, (size_t)nq * 4); memcpy(h + o_qlist, in->q_list, (size_t)nq * 4);
+  { int64_t* w = (int64_t*)(h + o_qaoff); for (int64_t i = 0; i <= nq; i++) w[i] = in->q_alt_off[i] - q0; }
+  memcpy(h + o_koff, k_off.data(), ((size_t)nq + 1) * 8); 
+  if (thread_form) memcpy(h + o_eoff, e_off.data(), ((size_t)nq + 1) * 8); else memset(h + o_eoff, 0, ((size_t)nq + 1) * 8);
+  if (v_bytes) memcpy(h + o_valt, in->v_alt_pool + v0, (size_t)v_bytes);
+  if (q_bytes) memcpy(h + o_qalt, in->q_alt_pool + q0, (size_t)q_bytes);
+  memset(h + o_valt + v_bytes, 0, 32); memset(h + o_qalt + q_bytes, 0, 32);
+  PopView v{};
+  v.pctseq = cfg->combine_pctseq; v.combine_match = cfg->combine_match; v.combine_match_max = cfg->combine_match_max; v.n_queries = nq;
+  v.list_off = (const int64_t*)(d + o_loff); v.list_is_ins = d + o_lins;
+  v.v_pos = (const int32_t*)(d + o_vpos); v.v_svlen = (const int32_t*)(d + o_vlen); v.v_alt_off = (const int64_t*)(d + o_vaoff); v.v_alt_pool = d + o_valt;
+  v.q_pos = (const int32_t*)(d + o_qpos); v.q_svlen = (const int32_t*)(d + o_qlen); v.q_list = (const int32_t*)(d + o_qlist);
+  v.q_alt_off = (const int64_t*)(d + o_qaoff); v.q_alt_pool = d + o_qalt;
+  v.k_off = (const int64_t*)(d + o_koff); v.carry = (int8_t*)(d + o_carry); v.e_off = (const int64_t*)(d + o_eoff); v.ed_scratch = (uint64_t*)(d + o_edscr);
+  v.out_best = (int32_t*)(d + o_best); v.out_dist = (int32_t*)(d + o_dist); v.stats = (unsigned long long*)(d + o_stats);
+  hipStream_t st = A.stream;
+  bool ok = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st) == hipSuccess;
+  ok = ok && hipMemsetAsync(d + o_stats, 0, 3 * 64 * 16 * sizeof(unsigned long long), st) == hipSuccess;
+  ok = ok && hipEventRecord(A.ev0, st) == hipSuccess;
+  if (ok) {
+    if (thread_form) hipLaunchKernelGGL(popmatch, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, st, v, nq);
+    else hipLaunchKernelGGL(popmatch_wave, dim3((unsigned)(nq < 65536 ? nq : 65536)), dim3(64), 0, st, v, nq);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  ok = ok && hipEventRecord(A.ev1, st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(h + o_best, d + o_best, o_stats + 3 * 64 * 16 * sizeof(unsigned long long) - o_best, hipMemcpyDeviceToHost, st) == hipSuccess;
+  ok = ok && hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) return 1;
+  { float ms = 0; if (hipEventElapsedTime(&ms, A.ev0, A.ev1) == hipSuccess) A.last_kernel_ms = ms; }
+  {
+    const unsigned long long* hs = (const unsigned long long*)(h + o_stats);
+    for (int c = 0; c < 3; c++) { unsigned long long t = 0; for (int k = 0; k < 64; k++) t += hs[(c * 64 + k) * 16]; A.last_stats[c] = (long long)t; }
+    A.last_stats[3] = (long long)in_end;
+  }
+  memcpy(in->out_best, h + o_best, (size_t)nq * 4);
+  memcpy(in->out_dist, h + o_dist, (size_t)nq * 4);
+  return 0;
+}
+
+// measurement hook of snf_population_match_batch: same meaning as snf_combine_last_stats
+extern "C" int snf_population_last_stats(int device, double* kernel_ms, int64_t* stats4) {
+  if (device < 0 || device >= SNF_MAX_DEVICES || !kernel_ms || !stats4) return 1;
+  DevArena& A = g_popmatch_arenas[device];
   std::lock_guard<std::mutex> hold(A.mu);
   *kernel_ms = A.last_kernel_ms;
   for (int k = 0; k < 4; k++) stats4[k] = A.last_stats[k];

@@ -22,6 +22,7 @@ static PyObject *S_svtype[7], *S_alt_sym[7], *S_N;
 static PyObject *K_contig, *K_pos, *K_id, *K_ref, *K_alt, *K_qual, *K_filter, *K_info, *K_svtype, *K_svlen, *K_end, *K_genotypes,
     *K_precise, *K_support, *K_rnames, *K_qc, *K_nm, *K_postprocess, *K_svlens, *K_fwd, *K_rev, *K_fds, *K_cov_up, *K_cov_dn,
     *K_cov_st, *K_cov_ce, *K_cov_en, *K_sample, *K_bnd_info, *K_sup_inline, *K_sup_splits, *K_raw, *K_raw_idx;
+static PyObject *I_POPULATION_AF, *I_POPULATION_SIZE;
 static PyObject *I_CHR2, *I_SUPPORT_LONG, *I_SUPPORT_SA, *I_STDEV_POS, *I_STDEV_LEN, *I_COVERAGE_VAR, *I_PHASE, *I_VAF;
 static PyObject *F_n, *F_m1, *F_m2, *F_last;
 static PyObject *S_dot, *S_comma, *O_zero, *T_none2, *I_COVERAGE;
@@ -899,6 +900,7 @@ typedef struct {
   const char* prefix; size_t prefix_len; const char* fmt; size_t fmt_len;
   const int32_t** dn_ptr; const Py_ssize_t* dn_len; const int32_t* EBT; const int64_t* EBS; long long cvx_cb, cvx_bs;
   int t_phase, t_symbolic, t_mosaic, t_nm; long long t_minsvlen;
+  const double* POP_AF; const int64_t* POP_SZ;      /* --combine-population: per emitted group (NULL: no population; NaN: nothing matched) */
 } FmtCtx;
 typedef struct { const FmtCtx* c; Py_ssize_t e0, e1; OutBuf tb; int64_t* off; const char* err; } FmtJob;      /* off: e1 - e0 + 1 offsets inside tb */
 
@@ -1048,7 +1050,10 @@ static void fmt_range(FmtJob* J) {
             if (!bad) bad = o->cov[q] == SNF_NONE_I32 ? QB_LIT(tb, "None") : qb_ll(tb, o->cov[q]);
           }
           if (!bad) bad = QB_LIT(tb, ";STRAND=") || (o->fwd > 0 && QB_LIT(tb, "+")) || (o->rev > 0 && QB_LIT(tb, "-")) || (c->t_nm && QB_LIT(tb, ";NM=-1"));
-          if (!bad && ns > 1) bad = QB_LIT(tb, ";AC=") || qb_ll(tb, t_ac);      /* call.info, sorted: AC, STDEV_LEN, STDEV_POS, SUPP_VEC */
+          if (!bad && ns > 1) bad = QB_LIT(tb, ";AC=") || qb_ll(tb, t_ac);      /* call.info, sorted: AC, POPULATION_*, STDEV_LEN, STDEV_POS, SUPP_VEC */
+          if (!bad && c->POP_AF)      /* sv.py:475-479: (round(af, 5), size), or the ints (0, 0) when nothing matched */
+            bad = QB_LIT(tb, ";POPULATION_AF=") || (isnan(c->POP_AF[e]) ? QB_LIT(tb, "0") : qb_f3(tb, c->POP_AF[e])) || QB_LIT(tb, ";POPULATION_SIZE=") ||
+                  qb_ll(tb, c->POP_SZ[e]);
           if (!bad) {
             if (o->n < 2) bad = QB_LIT(tb, ";STDEV_LEN=0;STDEV_POS=0");
             else bad = QB_LIT(tb, ";STDEV_LEN=") || qb_f3(tb, o->stdev_len) || QB_LIT(tb, ";STDEV_POS=") || qb_f3(tb, o->stdev_pos);
@@ -1072,11 +1077,13 @@ out:
 static void* fmt_thread(void* arg) { fmt_range((FmtJob*)arg); return NULL; }
 
 static PyObject* py_group_calls(PyObject* self, PyObject* args) {
-  PyObject *cls, *fds_cls, *objs, *block_cov, *prefix, *topt = Py_None, *covx = Py_None;
+  PyObject *cls, *fds_cls, *objs, *block_cov, *prefix, *topt = Py_None, *covx = Py_None, *popo = Py_None;
   Py_buffer ob, eb, gb, mb, cb, svb, tkb, sidb, sposb, evo, evb, evn, csb;
+  /* popo (optional): (af: float64 per emitted group, NaN = nothing matched; size: int64 per emitted group) of --combine-population */
+  Py_buffer pop_af, pop_sz; int have_pop = 0; const double* POP_AF = NULL; const int64_t* POP_SZ = NULL;
   long long null_min; int single;
-  if (!PyArg_ParseTuple(args, "OOO!y*y*y*y*y*y*y*y*y*O!y*y*y*LUpy*|OO", &cls, &fds_cls, &PyList_Type, &objs, &ob, &eb, &gb, &mb, &cb, &svb, &tkb, &sidb,
-                        &sposb, &PyList_Type, &block_cov, &evo, &evb, &evn, &null_min, &prefix, &single, &csb, &topt, &covx))
+  if (!PyArg_ParseTuple(args, "OOO!y*y*y*y*y*y*y*y*y*O!y*y*y*LUpy*|OOO", &cls, &fds_cls, &PyList_Type, &objs, &ob, &eb, &gb, &mb, &cb, &svb, &tkb, &sidb,
+                        &sposb, &PyList_Type, &block_cov, &evo, &evb, &evn, &null_min, &prefix, &single, &csb, &topt, &covx, &popo))
     return NULL;
   /* covx (dict, optional): the `_COVERAGE` dicts of the blocks as dense vectors - dense[task][sample] = int32 depth per bin of `cb`
    * bp (-1: no entry), eb_task / eb_start = task and start of every block of `block_cov`.  A lookup `block["_COVERAGE"][bin]`
@@ -1149,6 +1156,14 @@ static PyObject* py_group_calls(PyObject* self, PyObject* args) {
   PyObject** sid_objs = NULL; uint8_t* present = NULL; int* head = NULL; PyObject** chain = NULL; Py_ssize_t cap = 0;
   Py_ssize_t* evx_row = NULL; long long* evx_idx = NULL; int64_t evx_cap = 0;
   PyObject* out = NULL;
+  if (popo != Py_None) {
+    if (!PyTuple_Check(popo) || PyTuple_GET_SIZE(popo) != 2) { PyErr_SetString(PyExc_TypeError, "group_calls: the population columns are (af, size)"); goto done; }
+    if (PyObject_GetBuffer(PyTuple_GET_ITEM(popo, 0), &pop_af, PyBUF_SIMPLE) != 0) goto done;
+    if (PyObject_GetBuffer(PyTuple_GET_ITEM(popo, 1), &pop_sz, PyBUF_SIMPLE) != 0) { PyBuffer_Release(&pop_af); goto done; }
+    have_pop = 1;
+    if (pop_af.len / 8 < ne || pop_sz.len / 8 < ne) { PyErr_SetString(PyExc_ValueError, "group_calls: population columns shorter than the emitted groups"); goto done; }
+    POP_AF = (const double*)pop_af.buf; POP_SZ = (const int64_t*)pop_sz.buf;
+  }
   if ((Py_ssize_t)(ob.len / sizeof(snf_group_out_t)) < ng || cb.len < nm || svb.len / 8 < ne || tkb.len / 8 < ne || evo.len / 8 < ne + 1 ||
       evb.len != evn.len || csb.len / 4 < nobj) { PyErr_SetString(PyExc_ValueError, "group_calls: table sizes do not match"); goto done; }
   if (fast_cols && ((Py_ssize_t)(fr_rec.len / sizeof(snf_group_cand_t)) < nobj || fr_st.len / 8 < nobj || fr_ln.len / 4 < nobj || fr_hp.len < nobj ||
@@ -1224,6 +1239,7 @@ static PyObject* py_group_calls(PyObject* self, PyObject* args) {
       c.EM_TASK = (const int32_t*)hd_task.buf; c.EM_TYP = (const int32_t*)hd_typ.buf; c.AOFF = (const int64_t*)hd_aoff.buf; c.apool = (const char*)hd_apool.buf;
       c.apool_len = hd_apool.len; c.dn_ptr = dn_ptr; c.dn_len = dn_len; c.EBT = EBT; c.EBS = EBS; c.cvx_cb = cvx_cb; c.cvx_bs = cvx_bs;
       c.t_phase = t_phase; c.t_symbolic = t_symbolic; c.t_mosaic = t_mosaic; c.t_nm = t_nm; c.t_minsvlen = t_minsvlen;
+      c.POP_AF = POP_AF; c.POP_SZ = POP_SZ;
       for (long t = 0; t < nthr; t++) {
         jobs[t].c = &c; jobs[t].e0 = ne * t / nthr; jobs[t].e1 = ne * (t + 1) / nthr;
         jobs[t].off = (int64_t*)calloc((size_t)(jobs[t].e1 - jobs[t].e0) + 1, 8);
@@ -1537,7 +1553,10 @@ static PyObject* py_group_calls(PyObject* self, PyObject* args) {
             }
           }
           if (!bad) bad = OB_LIT(&tb, ";STRAND=") || (o->fwd > 0 && OB_LIT(&tb, "+")) || (o->rev > 0 && OB_LIT(&tb, "-")) || (t_nm && OB_LIT(&tb, ";NM=-1"));
-          if (!bad && ns > 1) bad = OB_LIT(&tb, ";AC=") || ob_ll(&tb, t_ac);      /* call.info, sorted: AC, STDEV_LEN, STDEV_POS, SUPP_VEC */
+          if (!bad && ns > 1) bad = OB_LIT(&tb, ";AC=") || ob_ll(&tb, t_ac);      /* call.info, sorted: AC, POPULATION_*, STDEV_LEN, STDEV_POS, SUPP_VEC */
+          if (!bad && POP_AF)
+            bad = OB_LIT(&tb, ";POPULATION_AF=") || (isnan(POP_AF[e]) ? OB_LIT(&tb, "0") : ob_f3(&tb, POP_AF[e])) || OB_LIT(&tb, ";POPULATION_SIZE=") ||
+                  ob_ll(&tb, POP_SZ[e]);
           if (!bad) {
             if (o->n < 2) bad = OB_LIT(&tb, ";STDEV_LEN=0;STDEV_POS=0");
             else bad = OB_LIT(&tb, ";STDEV_LEN=") || ob_f3(&tb, o->stdev_len) || OB_LIT(&tb, ";STDEV_POS=") || ob_f3(&tb, o->stdev_pos);
@@ -1565,6 +1584,10 @@ static PyObject* py_group_calls(PyObject* self, PyObject* args) {
     if (!bad && !single) {
       bad = set_steal(info, I_STDEV_POS, o->n < 2 ? PyLong_FromLong(0) : PyFloat_FromDouble(o->stdev_pos)) ||
             set_steal(info, I_STDEV_LEN, o->n < 2 ? PyLong_FromLong(0) : PyFloat_FromDouble(o->stdev_len));
+    }
+    if (!bad && POP_AF) {      /* sv.py:475-479: a float and an int, or the two ints (0, 0) when nothing matched */
+      bad = set_steal(info, I_POPULATION_AF, isnan(POP_AF[e]) ? PyLong_FromLong(0) : PyFloat_FromDouble(POP_AF[e])) ||
+            set_steal(info, I_POPULATION_SIZE, PyLong_FromLongLong(POP_SZ[e]));
     }
     if (!bad) {
       PyObject* fd = PyDict_New();
@@ -1623,6 +1646,7 @@ done:
   if (dn_buf) { for (Py_ssize_t k = 0; k < dn_n; k++) PyBuffer_Release(&dn_buf[k]); free(dn_buf); }
   free(dn_ptr); free(dn_len);
   if (have_covx) { PyBuffer_Release(&ebtb); PyBuffer_Release(&ebsb); }
+  if (have_pop) { PyBuffer_Release(&pop_af); PyBuffer_Release(&pop_sz); }
   free(tb.p); free(t_off); free(t_pos);
   PyBuffer_Release(&ob); PyBuffer_Release(&eb); PyBuffer_Release(&gb); PyBuffer_Release(&mb); PyBuffer_Release(&cb); PyBuffer_Release(&svb);
   PyBuffer_Release(&tkb); PyBuffer_Release(&sidb); PyBuffer_Release(&sposb); PyBuffer_Release(&evo); PyBuffer_Release(&evb); PyBuffer_Release(&evn);
@@ -2147,6 +2171,7 @@ PyMODINIT_FUNC PyInit__snf_fast(void) {
   INTERN(K_sample, "sample_internal_id"); INTERN(K_bnd_info, "bnd_info"); INTERN(K_sup_inline, "support_inline");
   INTERN(K_sup_splits, "support_splits"); INTERN(K_raw, "raw_vcf_line"); INTERN(K_raw_idx, "raw_vcf_line_index");
   INTERN(I_CHR2, "CHR2"); INTERN(I_SUPPORT_LONG, "SUPPORT_LONG"); INTERN(I_SUPPORT_SA, "SUPPORT_SA"); INTERN(I_STDEV_POS, "STDEV_POS");
+  INTERN(I_POPULATION_AF, "POPULATION_AF"); INTERN(I_POPULATION_SIZE, "POPULATION_SIZE");
   INTERN(I_STDEV_LEN, "STDEV_LEN"); INTERN(I_COVERAGE_VAR, "COVERAGE_VAR"); INTERN(I_PHASE, "PHASE"); INTERN(I_VAF, "VAF");
   INTERN(B_mate_contig, "mate_contig"); INTERN(B_mate_ref_start, "mate_ref_start"); INTERN(B_is_first, "is_first"); INTERN(B_is_reverse, "is_reverse");
   INTERN(P_batch, "batch"); INTERN(P_index, "index"); INTERN(K_class, "__class__"); INTERN(K_lz, "_lz"); INTERN(K_lzi, "_lzi");

@@ -71,6 +71,10 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.snf_combine_call_groups.restype = C.c_int
     lib.snf_combine_last_stats.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.snf_combine_last_stats.restype = C.c_int
+    lib.snf_population_match_batch.argtypes = [C.POINTER(abi.snf_config_t), C.c_int, C.POINTER(abi.snf_popmatch_t)]
+    lib.snf_population_match_batch.restype = C.c_int
+    lib.snf_population_last_stats.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.snf_population_last_stats.restype = C.c_int
     u8p, i64p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
     lib.snf_consensus_batch.argtypes = [C.c_int, C.c_int, u8p, C.c_int64, C.c_int64, i64p, i32p, i32p, i32p, i64p, i64p, i32p, u8p, i64p]
     lib.snf_consensus_batch.restype = C.c_int
@@ -462,6 +466,56 @@ def combine_last_stats(device: int = 0) -> dict:
     ms, st = C.c_double(), (C.c_int64 * 4)()
     if lib.snf_combine_last_stats(device, C.byref(ms), st) != 0:
         raise SnifflesAmdError("snf_combine_last_stats failed")
+    return dict(kernel_ms=float(ms.value), alignments=int(st[0]), aligned_bytes=int(st[1]), dp_cells=int(st[2]), staged_bytes=int(st[3]))
+
+
+def population_match_batch(cfg, table: dict, queries: dict, device: int = 0):
+    """`PopulationSNF.get_population_AF` for a batch of merged calls (snf_population_match_batch), one launch.
+    `table`: the variant lists of a population file as a CSR - list_off (int64, n_lists + 1), list_is_ins (uint8 per list), v_pos,
+    v_svlen (int32 per variant), v_alt_off (int64, n_variants + 1), v_alt_pool (uint8) - what `snfp.PopulationSNF.table()` builds.
+    `queries`: pos, svlen, list (int32 per query; list -1: no list), alt_off (int64, n + 1), alt_pool (uint8).
+    Returns (best: int32 per query - index over all variants, -1 none -, dist: int32 per query)."""
+    lib = load()
+
+    def col(a, dt, at_least=1):
+        a = np.ascontiguousarray(np.asarray(a, dt).reshape(-1))
+        return a if len(a) >= at_least else np.concatenate((a, np.zeros(at_least - len(a), dt)))
+    list_off = col(table["list_off"], np.int64)
+    n_lists = len(list_off) - 1
+    is_ins = col(table["list_is_ins"], np.uint8)
+    v_pos, v_svlen = col(table["v_pos"], np.int32), col(table["v_svlen"], np.int32)
+    v_alt_off, v_pool = col(table["v_alt_off"], np.int64), col(table["v_alt_pool"], np.uint8)
+    n_variants = len(v_alt_off) - 1
+    q_alt_off = col(queries["alt_off"], np.int64)
+    n = len(q_alt_off) - 1
+    q_pos, q_svlen, q_list = col(queries["pos"], np.int32), col(queries["svlen"], np.int32), col(queries["list"], np.int32)
+    q_pool = col(queries["alt_pool"], np.uint8)
+    best, dist = np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.int32)
+    if n <= 0:
+        return best[:0], dist[:0]
+    if n_lists < 0 or int(list_off[-1]) != n_variants or len(is_ins) < n_lists or min(len(v_pos), len(v_svlen)) < n_variants \
+            or min(len(q_pos), len(q_svlen), len(q_list)) < n or len(v_pool) < int(v_alt_off[-1]) or len(q_pool) < int(q_alt_off[-1]):
+        raise ValueError("population_match_batch: table / query columns do not fit together")
+    p32, p64, p8 = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    arg = abi.snf_popmatch_t(
+        n_lists=n_lists, list_off=list_off.ctypes.data_as(p64), list_is_ins=is_ins.ctypes.data_as(p8), n_variants=n_variants,
+        v_pos=v_pos.ctypes.data_as(p32), v_svlen=v_svlen.ctypes.data_as(p32), v_alt_off=v_alt_off.ctypes.data_as(p64),
+        v_alt_pool=v_pool.ctypes.data_as(p8), n_queries=n, q_pos=q_pos.ctypes.data_as(p32), q_svlen=q_svlen.ctypes.data_as(p32),
+        q_list=q_list.ctypes.data_as(p32), q_alt_off=q_alt_off.ctypes.data_as(p64), q_alt_pool=q_pool.ctypes.data_as(p8),
+        out_best=best.ctypes.data_as(p32), out_dist=dist.ctypes.data_as(p32))
+    cs = abi.config_struct(cfg)
+    if lib.snf_population_match_batch(C.byref(cs), device, C.byref(arg)) != 0:
+        raise SnifflesAmdError("snf_population_match_batch failed (no HIP device, columns that do not fit together, or an insertion "
+                               "with svlen <= 0 in the population while combine_pctseq is non-zero)")
+    return best[:n], dist[:n]
+
+
+def population_last_stats(device: int = 0) -> dict:
+    """Kernel time and alignment counters of the last population_match_batch on `device` (as `combine_last_stats`)."""
+    lib = load()
+    ms, st = C.c_double(), (C.c_int64 * 4)()
+    if lib.snf_population_last_stats(device, C.byref(ms), st) != 0:
+        raise SnifflesAmdError("snf_population_last_stats failed")
     return dict(kernel_ms=float(ms.value), alignments=int(st[0]), aligned_bytes=int(st[1]), dp_cells=int(st[2]), staged_bytes=int(st[3]))
 
 

@@ -442,7 +442,12 @@ class CombineTask(Task):
         collected = [t._collect(samples_snf) for t in tasks]
         assigns = tasks[0]._resolve(tasks, [c for c, _ in collected])
         ids = set(samples_snf.keys())
-        return [t._replay(c, e, a, ids) for t, (c, e), a in zip(tasks, collected, assigns)]
+        out = [t._replay(c, e, a, ids) for t, (c, e), a in zip(tasks, collected, assigns)]
+        # --combine-population: `SVGroup.call` leaves the two INFO entries (sv.py:475-479) to this point - the calls of all tasks
+        # are annotated in one launch instead of one lookup per call
+        from . import snfp
+        snfp.annotate_calls([c for calls in out for c in calls], tasks[0].config, device=tasks[0].device)
+        return out
 
     def _resolve(self, tasks: list, chains_per_task: list) -> list:
         """Phase 2: all chains of all `tasks` in one `snf_combine_resolve_batch` call; per task {svtype: group numbers}."""

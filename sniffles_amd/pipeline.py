@@ -212,7 +212,12 @@ def combine(snf_paths, config, vcf_handle=None, sample_ids=None, device: int = 0
     (`sniffles:371-490`) for one process - headers (sample ids, contig lengths, format checks), one `CombineTask` per
     contig over `snf.SNFile` readers (group assignment on the GPU), calls of a task sorted by position
     (`CombineResult`), VCF records in task order.  Returns the combined calls.  `objects=False`: VCF only, the records formatted
-    straight from the group table when the writer can (`VCF.can_write_merged`) - the same text; returns []."""
+    straight from the group table when the writer can (`VCF.can_write_merged`) - the same text; returns [].
+    `config.combine_population` (a path or an opened `snfp.PopulationSNF`): every call gets POPULATION_AF / POPULATION_SIZE from
+    the best-matching variant of that file.  `config.dev_population_snf` (a path): the merged calls are also written there as a
+    population SNF (`--dev-population-snf`) - per task in emission order, before the sort by position.  That needs the calls as
+    objects: with `objects=False` they are built for this purpose (the VCF is still written from them, the same text) and []
+    is returned all the same."""
     import os
     config.mode = "combine"
     config.snf_input_info, readers = [], {}
@@ -242,7 +247,11 @@ def combine(snf_paths, config, vcf_handle=None, sample_ids=None, device: int = 0
     tasks = [parallel.CombineTask(id=task_id, sv_id=0, contig=contig, start=0, end=length - 1, config=config, device=device,
                                   regions=(getattr(config, "regions_by_contig", None) or {}).get(contig))
              for task_id, (contig, length) in enumerate(contig_lengths)]
-    if not objects and writer is not None and writer.can_write_merged():
+    pop_out = None
+    if getattr(config, "dev_population_snf", None):
+        from . import snfp
+        pop_out = snfp.PopulationWriter(config.dev_population_snf, config)
+    if not objects and pop_out is None and writer is not None and writer.can_write_merged():
         # VCF only: the merged records are formatted straight from the group table (vcf.VCF.write_merged) - the same text, no SVCall objects
         for part in parallel.CombineTask.execute_many(tasks, readers, text_writer=writer):
             writer.write_merged(part, sort=getattr(config, "sort", True))
@@ -252,6 +261,8 @@ def combine(snf_paths, config, vcf_handle=None, sample_ids=None, device: int = 0
         return []
     # all contigs share one group-assignment launch (a contig alone leaves most of the device idle)
     for task, calls in zip(tasks, parallel.CombineTask.execute_many(tasks, readers)):
+        if pop_out is not None:
+            pop_out.add_task(task.id, task.contig, calls)
         if getattr(config, "sort", True):
             calls = sorted(calls, key=lambda c: c.pos)
         if writer is not None:
@@ -261,7 +272,9 @@ def combine(snf_paths, config, vcf_handle=None, sample_ids=None, device: int = 0
     for f in readers.values():
         candstore.clear_columns(f)
         f.close()
-    return out
+    if pop_out is not None:
+        pop_out.finish([c for c, _ in contig_lengths])
+    return out if objects else []
 
 
 def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle, tandem_repeats=None, device: int = 0, reference=None) -> int:

@@ -12,6 +12,10 @@ Files written here are read by the reference and the other way round:
   `coverage_binsize_combine` bp and rounded) is computed on the GPU from the task's sparse read table
   (`snf_batch_block_coverage`, include/sniffles_amd.h) - the dense vector is never built, and there is no CPU fallback.
 
+* record classes other modules register (`register_record_class`: `sniffles.snfp.PopulationVariant`, the record of a population
+  SNF - `sniffles_amd.snfp.PopulationSNF` is the subclass that adds the header's `population` entry) are written and read the
+  same way.
+
 Everything else in this module is container I/O (gzip, pickle, JSON, file offsets), like the reference.
 """
 from __future__ import annotations
@@ -30,9 +34,28 @@ from typing import Optional
 from . import sv
 
 REF_MODULE = "sniffles.sv"
-_CLASSES = {"SVCall": sv.SVCall, "SVCallBNDInfo": sv.SVCallBNDInfo, "ForwardDifferenceWelford": sv.ForwardDifferenceWelford,
-            "SVCallPostprocessingInfo": sv.SVCallPostprocessingInfo}
+# record classes of this package by the (module, name) the reference pickles them under; `register_record_class` adds to it
+# (sniffles_amd.snfp: `sniffles.snfp.PopulationVariant`, the record of a population SNF)
+_REF_NAME = {sv.SVCall: (REF_MODULE, "SVCall"), sv.SVCallBNDInfo: (REF_MODULE, "SVCallBNDInfo"),
+             sv.ForwardDifferenceWelford: (REF_MODULE, "ForwardDifferenceWelford"),
+             sv.SVCallPostprocessingInfo: (REF_MODULE, "SVCallPostprocessingInfo")}
+_BY_NAME = {}
+# stand-ins that carry the reference's module path: pickle writes a class as (module, qualname) and checks that the pair
+# resolves to the object it was given, so the records are written as instances of these (the record classes themselves are
+# never touched) while a module of that name holds them
+_PROXIES = {}
 _LOCK = threading.Lock()
+
+
+def register_record_class(module: str, name: str, cls) -> None:
+    """`cls` is written to SNF blocks as `module.name` (the reference's path) and read back from that name or its own."""
+    _REF_NAME[cls] = (module, name)
+    _BY_NAME[(module, name)] = _BY_NAME[(cls.__module__, name)] = cls
+    _PROXIES[(module, name)] = type(name, (), {"__module__": module, "__qualname__": name})
+
+
+for _cls, (_m, _n) in list(_REF_NAME.items()):
+    register_record_class(_m, _n, _cls)
 
 
 # what a block may name besides the record classes: containers / scalars of the standard library and numpy scalars (the
@@ -46,22 +69,17 @@ _SAFE_GLOBALS = {
 
 
 class _Unpickler(pickle.Unpickler):
-    """Blocks written by the reference name `sniffles.sv.*`; resolve them to this package's record types.  Only those
-    classes and a fixed list of harmless globals are accepted: an .snf file cannot make the reader import anything else."""
+    """Blocks written by the reference name `sniffles.sv.*` (a population SNF: `sniffles.snfp.PopulationVariant`); resolve them
+    to this package's record types.  Only those classes and a fixed list of harmless globals are accepted: an .snf file cannot
+    make the reader import anything else."""
 
     def find_class(self, module, name):
-        if module in (REF_MODULE, sv.__name__) and name in _CLASSES:
-            return _CLASSES[name]
+        cls = _BY_NAME.get((module, name))
+        if cls is not None:
+            return cls
         if (module, name) in _SAFE_GLOBALS:
             return super().find_class(module, name)
         raise pickle.UnpicklingError(f"SNF block names {module}.{name}: not a Sniffles record class - refusing to load it")
-
-
-_NAME_OF = {cls: name for name, cls in _CLASSES.items()}
-# stand-ins that carry the reference's module path: pickle writes a class as (module, qualname) and checks that the pair
-# resolves to the object it was given, so the records are written as instances of these (the record classes themselves are
-# never touched) while a module of that name holds them
-_PROXIES = {name: type(name, (), {"__module__": REF_MODULE, "__qualname__": name}) for name in _CLASSES}
 
 
 class _RefPickler(pickle.Pickler):
@@ -70,40 +88,48 @@ class _RefPickler(pickle.Pickler):
         self._classes = classes
 
     def reducer_override(self, obj):
-        name = _NAME_OF.get(type(obj))
-        if name is None:
+        ref = _REF_NAME.get(type(obj))
+        if ref is None:
             return NotImplemented
         import copyreg
         # (copyreg.__newobj__ insists on the object's own class; _reconstructor is object.__new__(cls) as well)
-        return copyreg._reconstructor, (self._classes[name], object, None), obj.__dict__
+        return copyreg._reconstructor, (self._classes[ref], object, None), obj.__dict__
 
 
 def _dumps_as_reference(block: dict) -> bytes:
     """pickle.dumps of a block with this package's record classes written under the reference's names.
 
-    When the real `sniffles.sv` is loaded in this process its classes are named directly.  Otherwise the pickler must still
-    find, under `sniffles.sv`, the class object it is asked to write: for the duration of the dump a stand-in module of that
-    name holds proxy classes (`_PROXIES`).  The record classes of this package are not modified at any time."""
+    Where the real reference module (`sniffles.sv`, `sniffles.snfp`) is loaded in this process its classes are named directly.
+    Otherwise the pickler must still find, under that name, the class object it is asked to write: for the duration of the dump
+    a stand-in module of that name holds proxy classes (`_PROXIES`).  The record classes of this package are not modified at
+    any time."""
     with _LOCK:
-        real = sys.modules.get(REF_MODULE)
         buf = io.BytesIO()
-        if real is not None and getattr(real, "__file__", None):
-            _RefPickler(buf, {name: getattr(real, name) for name in _CLASSES}).dump(block)
-            return buf.getvalue()
+        classes, put = {}, []
         had_pkg = "sniffles" in sys.modules
         try:
-            if not had_pkg:
-                pkg = types.ModuleType("sniffles")
-                pkg.__path__ = []
-                sys.modules["sniffles"] = pkg
-            mod = types.ModuleType(REF_MODULE)
-            for name, proxy in _PROXIES.items():
-                setattr(mod, name, proxy)
-            sys.modules[REF_MODULE] = mod
-            _RefPickler(buf, _PROXIES).dump(block)
+            for module in sorted({m for m, _ in _PROXIES}):
+                names = [n for m, n in _PROXIES if m == module]
+                real = sys.modules.get(module)
+                if real is not None and getattr(real, "__file__", None):
+                    for n in names:
+                        classes[(module, n)] = getattr(real, n)
+                    continue
+                if "sniffles" not in sys.modules:
+                    pkg = types.ModuleType("sniffles")
+                    pkg.__path__ = []
+                    sys.modules["sniffles"] = pkg
+                mod = types.ModuleType(module)
+                for n in names:
+                    setattr(mod, n, _PROXIES[(module, n)])
+                    classes[(module, n)] = _PROXIES[(module, n)]
+                put.append(module)
+                sys.modules[module] = mod
+            _RefPickler(buf, classes).dump(block)
             return buf.getvalue()
         finally:
-            sys.modules.pop(REF_MODULE, None)
+            for module in put:
+                sys.modules.pop(module, None)
             if not had_pkg:
                 sys.modules.pop("sniffles", None)
 
@@ -136,8 +162,7 @@ def _empty_block() -> dict:
     return block
 
 
-def _header_line(config, index: dict, candidate_count: int) -> bytes:
-    doc = {"config": config.__dict__, "index": index, "snf_candidate_count": candidate_count}
+def _header_line(doc: dict) -> bytes:
     return (json.dumps(doc, default=lambda obj: "<Unstored_Object>") + "\n").encode()
 
 
@@ -284,12 +309,15 @@ class SNFileBase:
             means[c] = sum(values) / len(values) if values else 0
         return means
 
+    def _create_header(self, config, main_index: dict, snf_candidate_count: int) -> dict:
+        return {"config": config.__dict__, "index": main_index, "snf_candidate_count": snf_candidate_count}
+
     def write_results(self, config, contigs) -> int:
         """Header, then the part files in task order (each is removed); returns the candidate count (snf.py:186-223)."""
         parts = sorted(self._results, key=lambda r: r.task_id)
         count = sum(r.snf_candidate_count for r in parts)
         config.contig_coverages = self._calculate_contig_coverages(contigs)
-        self.handle.write(_header_line(config, _shifted_index(parts), count))
+        self.handle.write(_header_line(self._create_header(config, _shifted_index(parts), count)))
         for part in parts:
             with open(part.snf_filename, "rb") as h:
                 self.handle.write(h.read())

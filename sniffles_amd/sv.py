@@ -709,6 +709,8 @@ class SVGroup:
         if abs(call.svlen) < config.minsvlen_screen:
             return None
         task.sv_id += 1
+        # (POPULATION_AF / POPULATION_SIZE, sv.py:475-479: set for all calls of a merge at once by the caller -
+        # `CombineTask._execute_many_objects` / `snfp.annotate_calls` - instead of one population lookup per call)
         return call
 
 
