@@ -683,7 +683,8 @@ SNF_FILES = {
 
 
 # ---------------------------------------------------------------------------------------------- signature extraction
-# name -> dict(gen=kwargs of synth_bam.gen_records | fixture=file under tests/golden, contig, region, read_id_offset,
+# name -> dict(gen=kwargs of synth_bam.gen_records | fixture=file under tests/golden | build=table of tests/extract_edges.py,
+#              contig, region, read_id_offset,
 #              args=reference command line, overrides=attributes set on the reference config afterwards,
 #              cfg=the same settings as sniffles_amd / oracle extraction config keywords)
 EXTRACT = {
@@ -717,6 +718,15 @@ EXTRACT = {
                                args=(), overrides={}, cfg={}),
     "extract_hg002_chr1": dict(fixture="bam_hg002.bam.gz", contig="chr1", region=(72000000, 73000000), read_id_offset=0,
                                args=(), overrides={}, cfg={}),
+    # directed tables (tests/extract_edges.py): the internal edges of the extraction kernels.  The `cigar` table brings its region
+    # (records and events lie on both ends of it), an odd long_ins_length and a sequence cache its insertions straddle
+    "extract_edges_cigar": dict(build="cigar", contig="c1", region=(50000, 250000), read_id_offset=3,
+                                args=("--long-ins-length", "2501", "--dev-seq-cache-maxlen", "400"), overrides={},
+                                cfg=dict(long_ins_length=2501, dev_seq_cache_maxlen=400)),
+    "extract_edges_sa": dict(build="sa", contig="c1", region=(0, 400000), read_id_offset=0, args=(), overrides={}, cfg={}),
+    "extract_edges_sa_many_splits": dict(build="sa", contig="c1", region=(0, 400000), read_id_offset=0,
+                                         args=("--max-splits-base", "100"), overrides={}, cfg=dict(max_splits_base=100)),
+    "extract_edges_tags": dict(build="tags", contig="c1", region=(0, 400000), read_id_offset=0, args=(), overrides={}, cfg={}),
 }
 
 
@@ -728,6 +738,9 @@ def extract_records(case):
     if "fixture" in case:
         with gzip.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", case["fixture"]), "rb") as f:
             return bam.parse_bam(f.read())
+    if "build" in case:
+        import extract_edges
+        return extract_edges.BUILDERS[case["build"]]()
     names, lens, recs = synth_bam.gen_records(**case["gen"])
     return bam.records_from_list(names, lens, recs)
 

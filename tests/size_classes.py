@@ -2,7 +2,8 @@
 tests/test_knobs.py reads the switches), and the ladders t - 1, t, t + 1 the directed cases of tests/cases.py and
 tests/test_size_classes.py are derived from.  A threshold that is no longer found is an error, not a default: a case that
 silently tests the middle of a class is what this module is there to prevent.  ed_thresholds(): the same for the edit-distance
-kernels and the merge kernel that calls them (tests/ed_edges.py, tests/test_edit_distance_edges.py)."""
+kernels and the merge kernel that calls them (tests/ed_edges.py, tests/test_edit_distance_edges.py).  extract_thresholds(): the same
+for the extraction kernels (tests/extract_edges.py, tests/test_extract_edges.py)."""
 import os
 import re
 
@@ -78,6 +79,53 @@ def ed_thresholds():
         ed_wave_grid=int(ed_grid[0]), combine_wave_grid=int(cb_grid[0]),
         carry_min_len=int(_one(r"k_off\[p \+ 1\] = k_off\[p\] \+ \(maxlen > (\d+) \? maxlen \+ 8 : 8\);", combine,
                                "the carry sizing rule of snf_combine_resolve_batch")),
+    )
+
+
+def extract_thresholds():
+    """dict of the literals at which the extraction kernels (snf_extract.hip) change what a lane, a step, a chunk or a block holds, and
+    of the defaults of the two switches that select the wave form's grid and instance (snf_knobs.h).  `step` is derived: the CIGAR
+    operations a wave takes per step."""
+    x, knobs = _src("snf_extract.hip"), _src("snf_knobs.h")
+    clip = _one(r"const int k = lane < (\d+) \? lane : n_cig - 1 - \(lane - (\d+)\);\n\s*if \(lane < (\d+) \? k < n_cig : \(lane < (\d+) && k >= 1\)\)", x,
+                "the clip lanes of extract_record")
+    if not (clip[0] == clip[1] == clip[2]):
+        raise AssertionError(f"size_classes: the lanes of the leading clip operations are written as different numbers {clip}")
+    fold = _one(r"double a\[(\d+)\], nx\[(\d+)\];", x, "the registers of x_nmsum's fold")
+    fold_step = _one(r"for \(int k0 = 0; k0 < cnt; k0 \+= (\d+)\) \{", x, "the step of x_nmsum's fold")
+    if not (fold[0] == fold[1] == fold_step):
+        raise AssertionError(f"size_classes: the width of x_nmsum's fold is written as different numbers {fold + (fold_step,)}")
+    blocks = re.findall(r"hipLaunchKernelGGL\(x_(?:count|emit), dim3\(\(unsigned\)\(\(n \+ (\d+)\) / (\d+)\)\), dim3\((\d+)\), 0, 0, v, n\);", x)
+    if len(blocks) != 2:
+        raise AssertionError(f"size_classes: expected the two thread-form launches of snf_extract.hip, found {len(blocks)}")
+    sizes = {int(b[0]) + 1 for b in blocks} | {int(v) for b in blocks for v in b[1:]}
+    if len(sizes) != 1:
+        raise AssertionError(f"size_classes: the block size of the thread-form launches is written as different numbers {blocks}")
+    opl = int(_one(r"constexpr int OPL = WAVE \? (\d+) : 1;", x, "OPL"))
+    comma = _one(r"for \(int32_t k0 = ea; k0 < eb; k0 \+= (\d+)\) \{\n[^\n]*\n[^\n]*\n\s*if \(eb - k0 < (\d+)\) z &= \(1ull << \((\d+) \* \(eb - k0\)\)\) - 1ull;", x,
+                 "the word of the comma scanner")
+    if len(set(comma)) != 1:
+        raise AssertionError(f"size_classes: the word of the comma scanner is written as different numbers {comma}")
+    launch = re.search(r"template <bool EMIT> void x_launch_wave\(int waves, unsigned grid, const ExView& v, int64_t n\) \{\n(.*?)\n\}", x, re.S)
+    if not launch:
+        raise AssertionError("size_classes: x_launch_wave is no longer found in snf_extract.hip")
+    instances = [int(w) for w in re.findall(r"x_wave<EMIT, (\d+)>", launch.group(1))]
+    if len(instances) < 2 or len(set(instances)) != len(instances):
+        raise AssertionError(f"size_classes: the instances of x_launch_wave read as {instances}")
+    return dict(
+        comma_word=int(comma[0]), wave_instances=tuple(sorted(instances)),
+        nul_chunk=int(_one(r"x_find_nul\(const uint8_t\* blob, int64_t p, int64_t end, int lane\) \{\n\s*const int W = WAVE \? (\d+) : 1;\n\s*for \(int64_t q = p; q < end; q \+= W\)",
+                           x, "the chunk of x_find_nul")),
+        xmaxseg=_define("XMAXSEG", "snf_extract.hip"), xauxcap=_define("XAUXCAP", "snf_extract.hip"),
+        nm_chunk=_define("X_NM_CHUNK", "snf_extract.hip"), ahead=_define("X_AHEAD", "snf_extract.hip"),
+        opl=opl, step=WAVE * opl,
+        sa_chunk=int(_one(r"for \(int32_t c0 = 0; c0 <= sa_len; c0 \+= (\d+)\) \{", x, "the chunk of the SA cutter")),
+        clip_lanes=int(clip[0]), clip_lanes_end=int(clip[3]),
+        nm_fold=int(fold_step), thread_block=sizes.pop(),
+        blob_pad=int(_one(r"v\.blob = x_up\(x->dev, in->records, \(size_t\)in->records_len, (\d+)\);", x, "the blob padding of do_upload")),
+        grid_cap=1 << int(_one(r'int grid_cap = env_set\("SNF_EXTRACT_GRID"\) \? env_pos\("SNF_EXTRACT_GRID", 1\) : \(1 << (\d+)\);', knobs,
+                               "the default grid cap of the wave form")),
+        waves=int(_one(r'int waves = env_int\("SNF_EXTRACT_WAVES", (\d+)\);', knobs, "the default of SNF_EXTRACT_WAVES")),
     )
 
 
