@@ -725,6 +725,64 @@ int snf_extract_device_view(snf_extract_t* x, snf_task_input_t* out, int* device
 void snf_extract_destroy(snf_extract_t* x);
 const char* snf_extract_last_error(void);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The container layer on the device (csrc/snf_bgzf.h): the compressed bytes of a run of BGZF members -> the inflated
+ * BAM stream in HBM -> the record boundaries -> per record its first six dwords and its read name.  The reference
+ * counterpart is pysam / htslib's BGZF reader and record iterator behind `bam.fetch` (leadprov.py:487).  The host keeps
+ * the container bookkeeping: it hops through the member headers (BSIZE) for the member table and parses the BAM header
+ * (inflated with zlib from the leading members) for the initial carry.  CRC-32 is not checked.
+ * Additive to ABI version 5.
+ */
+typedef struct snf_bgzf_member {
+  int64_t payload_off;      /* offset of the member's deflate payload in the compressed bytes */
+  int64_t out_off;          /* offset of its output in the inflated stream of this run: the exclusive sum of isize */
+  uint32_t payload_len;
+  uint32_t isize;           /* at most 65536 */
+} snf_bgzf_member_t;
+
+typedef struct snf_bam_carry {   /* state of the record chain between two runs of members */
+  int64_t skip;             /* bytes still to skip before the next block_size field (initially: what is left of the BAM header) */
+  int64_t count;            /* records counted so far */
+  int64_t stream_pos;       /* inflated bytes in front of the run */
+  int64_t origin;           /* rec_off values are stream positions minus this (the BAM header's length: parse_bam's offsets) */
+  uint8_t part[3];          /* bytes of a block_size field that straddles the border */
+  uint8_t n_part;
+  int32_t _pad;
+} snf_bam_carry_t;
+
+typedef struct snf_bgzf_result {
+  int64_t stream_len;       /* inflated bytes of this run */
+  int64_t n_records;        /* records whose block_size field ended in this run */
+  const int64_t* rec_off;   /* host, n_records + 1: the last entry is the end of the run */
+  const uint32_t* heads;    /* host, n_records x 6: block_size, refID, pos, l_read_name|mapq|bin, n_cigar_op|flag, l_seq
+                               (all zero for a record whose head is cut by the end of the run) */
+  const uint8_t* names;     /* host, n_records x name_width: the read names, NUL-padded */
+  int32_t name_width;       /* the largest l_read_name of the run */
+  int32_t device;
+  snf_bam_carry_t carry;    /* what the next run starts from; the stream ended cleanly iff skip == 0 and n_part == 0 */
+  const uint8_t* d_stream;  /* DEVICE: the inflated stream (stream_len bytes + at least 16 bytes of padding) */
+  const int64_t* d_rec_off; /* DEVICE: the same n_records + 1 offsets */
+  float ms_inflate, ms_chain;   /* kernel times (HIP events) */
+} snf_bgzf_result_t;
+
+typedef struct snf_bgzf snf_bgzf_t;
+int snf_bgzf_create(int device, snf_bgzf_t** out);
+/* A malformed member fails the call: "BGZF member <index>: <reason>", the first one in file order; a block_size below 32:
+ * "truncated BAM record at byte <stream position>".  The handle stays usable. */
+int snf_bgzf_inflate(snf_bgzf_t* z, const uint8_t* compressed, int64_t compressed_len, const snf_bgzf_member_t* members,
+                     int64_t n_members, const snf_bam_carry_t* carry_in);
+int snf_bgzf_result(snf_bgzf_t* z, snf_bgzf_result_t* out);   /* library-owned until the next inflate / destroy */
+int snf_bgzf_read_stream(snf_bgzf_t* z, int64_t off, int64_t len, uint8_t* dst);   /* inflated bytes back to the host (tests) */
+void snf_bgzf_destroy(snf_bgzf_t* z);
+const char* snf_bgzf_last_error(void);
+
+/* snf_extract_upload for a blob and a record table that are in HBM already (an snf_bgzf_t's, which must outlive the use):
+ * in->records and in->rec_off are DEVICE pointers on `device` - rec_off may point into the middle of the file's table, its
+ * offsets are relative to in->records; in->qname_rank and the contig tables are host pointers.  `heads`: host, n_records x 6 as
+ * above; the checks, the dispatch order and algo_bytes of snf_extract_upload are computed from it (same refusals, same words).
+ * The extraction does not own the attached memory.  A `device` other than the handle's is refused. */
+int snf_extract_attach_device(snf_extract_t* x, const snf_extract_input_t* in, const uint32_t* heads, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -430,6 +430,26 @@ class snf_extract_result_t(C.Structure):
                 ("algo_bytes", i64)]
 
 
+# ---- BGZF inflate and record chain on the device (snf_bgzf_*, csrc/snf_bgzf.h)
+class snf_bgzf_member_t(C.Structure):
+    _fields_ = [("payload_off", i64), ("out_off", i64), ("payload_len", C.c_uint32), ("isize", C.c_uint32)]
+
+
+BGZF_MEMBER_DTYPE = np.dtype([("payload_off", "<i8"), ("out_off", "<i8"), ("payload_len", "<u4"), ("isize", "<u4")])
+assert BGZF_MEMBER_DTYPE.itemsize == C.sizeof(snf_bgzf_member_t) == 24
+
+
+class snf_bam_carry_t(C.Structure):
+    _fields_ = [("skip", i64), ("count", i64), ("stream_pos", i64), ("origin", i64), ("part", C.c_uint8 * 3), ("n_part", C.c_uint8),
+                ("_pad", i32)]
+
+
+class snf_bgzf_result_t(C.Structure):
+    _fields_ = [("stream_len", i64), ("n_records", i64), ("rec_off", C.POINTER(C.c_int64)), ("heads", C.POINTER(C.c_uint32)),
+                ("names", u8p), ("name_width", i32), ("device", i32), ("carry", snf_bam_carry_t), ("d_stream", C.c_void_p),
+                ("d_rec_off", C.c_void_p), ("ms_inflate", C.c_float), ("ms_chain", C.c_float)]
+
+
 def extract_config_struct(cfg) -> snf_extract_config_t:
     """`cfg`: anything with the SnifflesConfig attribute names extraction reads (config.py:190-215, 507-617)."""
     g = lambda name, default: getattr(cfg, name, default)

@@ -1017,6 +1017,7 @@ SNF_HD void x_totals_body(int64_t i, const ExView& v) {
 }
 
 }  // namespace snf
+#include "snf_bgzf.h"
 using namespace snf;
 SNF_KERNEL(x_count, ExView)
 SNF_KERNEL(x_emit, ExView)
@@ -1177,15 +1178,16 @@ template <bool EMIT> void x_launch_wave(int waves, unsigned grid, const ExView& 
   else hipLaunchKernelGGL((x_wave<EMIT, 4>), dim3(grid), dim3(64), 0, 0, v, n);
 }
 
-int do_upload(snf_extract* x, const snf_extract_input_t* in) {
-  if (!in || in->n_records < 0 || (in->n_records && (!in->records || !in->rec_off || !in->qname_rank))) snf::fail("extract input: null pointer");
-  if (in->n_contigs < 0 || (in->n_contigs && (!in->contig_hash || !in->contig_rank))) snf::fail("extract input: contig table missing");
+// What snf_extract_upload and snf_extract_attach_device share: the checks, the dispatch order and algo_bytes, computed from the first
+// 24 bytes of every record (`head(i)`) and the host copy of the offsets.  attached: the blob and the offsets are in HBM already.
+template <class Head>
+void x_take_input(snf_extract* x, const snf_extract_input_t* in, const int64_t* rec_off, Head head, bool attached) {
   for (int64_t i = 0; i < in->n_records; i++) {
-    const int64_t a = in->rec_off[i], b = in->rec_off[i + 1];
+    const int64_t a = rec_off[i], b = rec_off[i + 1];
     if (a < 0 || b < a + 36 || b > in->records_len) snf::fail("extract input: record offsets malformed at record " + std::to_string(i));
-    int32_t bs; memcpy(&bs, in->records + a, 4);
+    const uint8_t* R = head(i);
+    int32_t bs; memcpy(&bs, R, 4);
     if ((int64_t)bs + 4 != b - a) snf::fail("extract input: block_size of record " + std::to_string(i) + " disagrees with rec_off");
-    const uint8_t* R = in->records + a;
     uint16_t n_cig; int32_t l_seq; memcpy(&n_cig, R + 16, 2); memcpy(&l_seq, R + 20, 4);
     if (l_seq < 0 || 36 + (int64_t)R[12] + 4 * (int64_t)n_cig + ((int64_t)l_seq + 1) / 2 + l_seq > b - a)
       snf::fail("extract input: record " + std::to_string(i) + " shorter than its fixed fields say");
@@ -1197,8 +1199,11 @@ int do_upload(snf_extract* x, const snf_extract_input_t* in) {
   ExView& v = x->v;
   v = ExView{};
   v.cfg = x->cfg;
-  v.blob = x_up(x->dev, in->records, (size_t)in->records_len, 16);
-  v.rec_off = x_up(x->dev, in->rec_off, (size_t)in->n_records + 1);
+  if (attached) { v.blob = in->records; v.rec_off = in->rec_off; }      // (not ours: never freed here)
+  else {
+    v.blob = x_up(x->dev, in->records, (size_t)in->records_len, 16);
+    v.rec_off = x_up(x->dev, in->rec_off, (size_t)in->n_records + 1);
+  }
   v.qname_rank = x_up(x->dev, in->qname_rank, (size_t)in->n_records);
   v.ctg_hash = x_up(x->dev, in->contig_hash, (size_t)in->n_contigs);
   v.ctg_rank = x_up(x->dev, in->contig_rank, (size_t)in->n_contigs);
@@ -1206,7 +1211,7 @@ int do_upload(snf_extract* x, const snf_extract_input_t* in) {
     const int64_t n = in->n_records;
     std::vector<uint32_t> cnt(65538, 0), ord((size_t)(n ? n : 1));
     auto key = [&](int64_t i) -> uint32_t {
-      const uint8_t* R = in->records + in->rec_off[i];
+      const uint8_t* R = head(i);
       int32_t rid; uint16_t nc; memcpy(&rid, R + 4, 4); memcpy(&nc, R + 16, 2);
       return rid == in->region_ref_id ? 65535u - nc : 65536u;
     };
@@ -1222,12 +1227,28 @@ int do_upload(snf_extract* x, const snf_extract_input_t* in) {
   // algorithmic input bytes: everything of a record of this contig except its sequence and quality bytes
   int64_t ab = 0;
   for (int64_t i = 0; i < in->n_records; i++) {
-    const uint8_t* R = in->records + in->rec_off[i];
+    const uint8_t* R = head(i);
     int32_t rid, l_seq; memcpy(&rid, R + 4, 4); memcpy(&l_seq, R + 20, 4);
-    ab += (rid == in->region_ref_id) ? (in->rec_off[i + 1] - in->rec_off[i]) - ((int64_t)l_seq + 1) / 2 - l_seq : 36;
+    ab += (rid == in->region_ref_id) ? (rec_off[i + 1] - rec_off[i]) - ((int64_t)l_seq + 1) / 2 - l_seq : 36;
   }
   x->res.algo_bytes = ab;
   x->have_input = true;
+}
+
+int do_upload(snf_extract* x, const snf_extract_input_t* in) {
+  if (!in || in->n_records < 0 || (in->n_records && (!in->records || !in->rec_off || !in->qname_rank))) snf::fail("extract input: null pointer");
+  if (in->n_contigs < 0 || (in->n_contigs && (!in->contig_hash || !in->contig_rank))) snf::fail("extract input: contig table missing");
+  x_take_input(x, in, in->rec_off, [&](int64_t i) { return in->records + in->rec_off[i]; }, false);
+  return 0;
+}
+
+int do_attach(snf_extract* x, const snf_extract_input_t* in, const uint32_t* heads, int device) {
+  if (!in || in->n_records < 0 || (in->n_records && (!in->records || !in->rec_off || !in->qname_rank || !heads))) snf::fail("extract input: null pointer");
+  if (in->n_contigs < 0 || (in->n_contigs && (!in->contig_hash || !in->contig_rank))) snf::fail("extract input: contig table missing");
+  if (device != x->device) snf::fail("extract input: the attached records are on device " + std::to_string(device) + ", the handle on device " + std::to_string(x->device));
+  std::vector<int64_t> ro((size_t)in->n_records + 1, 0);
+  if (in->n_records) x_d2h(ro.data(), in->rec_off, ro.size() * 8);      // (8 bytes per record: the offsets the checks are made against)
+  x_take_input(x, in, ro.data(), [&](int64_t i) { return (const uint8_t*)(heads + 6 * i); }, true);
   return 0;
 }
 
@@ -1418,6 +1439,11 @@ int snf_extract_upload(snf_extract_t* x, const snf_extract_input_t* in) {
   if (hipSetDevice(x->device) != hipSuccess) { g_xerr = "hipSetDevice failed"; return 1; }
   X_TRY(do_upload(x, in))
 }
+int snf_extract_attach_device(snf_extract_t* x, const snf_extract_input_t* in, const uint32_t* heads, int device) {
+  if (!x) { g_xerr = "null handle"; return 1; }
+  if (hipSetDevice(x->device) != hipSuccess) { g_xerr = "hipSetDevice failed"; return 1; }
+  X_TRY(do_attach(x, in, heads, device))
+}
 int snf_extract_run(snf_extract_t* x) {
   if (!x) { g_xerr = "null handle"; return 1; }
   if (hipSetDevice(x->device) != hipSuccess) { g_xerr = "hipSetDevice failed"; return 1; }
@@ -1465,5 +1491,165 @@ void snf_extract_destroy(snf_extract_t* x) {
   if (x->ev_prep) (void)hipEventDestroy(x->ev_prep);
   if (x->side) (void)hipStreamDestroy(x->side);
   delete x;
+}
+}
+
+// ========================================================================== BGZF inflate + record chain: host side ====
+struct snf_bgzf {
+  int device = 0;
+  std::vector<void*> dev;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint8_t* d_stream = nullptr; int64_t* d_rec_off = nullptr;
+  std::vector<int64_t> h_rec_off; std::vector<uint32_t> h_heads; std::vector<uint8_t> h_names;
+  snf_bgzf_result_t res{};
+  bool have = false;
+};
+
+namespace {
+thread_local std::string g_zerr;
+
+void do_bgzf_inflate(snf_bgzf* z, const uint8_t* comp, int64_t comp_len, const snf_bgzf_member_t* mem, int64_t n_mem, const snf_bam_carry_t* cin) {
+  if (comp_len < 0 || n_mem < 0 || (comp_len && !comp) || (n_mem && !mem) || !cin) snf::fail("snf_bgzf_inflate: null argument");
+  if (cin->skip < 0 || cin->skip >= (1ll << 36) || cin->count < 0 || cin->n_part > 3 || (cin->n_part && cin->skip)) snf::fail("snf_bgzf_inflate: malformed carry");
+  int64_t total = 0;
+  for (int64_t m = 0; m < n_mem; m++) {
+    const snf_bgzf_member_t& b = mem[m];
+    if (b.payload_off < 0 || b.payload_off + (int64_t)b.payload_len > comp_len) snf::fail("BGZF member " + std::to_string(m) + ": payload outside the compressed bytes");
+    if (b.isize > BZ_WIN) snf::fail("BGZF member " + std::to_string(m) + ": ISIZE above 65536");
+    if (b.out_off != total) snf::fail("BGZF member " + std::to_string(m) + ": out_off is not the exclusive sum of ISIZE");
+    total += b.isize;
+  }
+  const BgzfKnobs k;
+  x_release(z->dev);
+  z->have = false; z->d_stream = nullptr; z->d_rec_off = nullptr;
+  const int64_t rec_cap = total / 36 + 2;      // a record is at least 36 bytes; one more for the end of the run
+  uint8_t* d_comp; snf_bgzf_member_t* d_mem; uint32_t* d_status; unsigned long long* d_carry; uint32_t* d_misc;
+  try {
+    d_comp = x_up(z->dev, comp, (size_t)comp_len, 16);
+    d_mem = x_up(z->dev, mem, (size_t)n_mem);
+    z->d_stream = x_alloc<uint8_t>(z->dev, (size_t)total, 64);
+    z->d_rec_off = x_alloc<int64_t>(z->dev, (size_t)rec_cap);
+    d_status = x_alloc<uint32_t>(z->dev, (size_t)n_mem);
+    d_carry = x_alloc<unsigned long long>(z->dev, 2 * (size_t)n_mem + 4);      // [2 (n_mem + 1)] .. : the error word
+    d_misc = x_alloc<uint32_t>(z->dev, 4);                                     // [0] ticket, [1] longest l_read_name
+  } catch (const snf::Error& e) {
+    x_release(z->dev);
+    snf::fail("the BAM's " + std::to_string((long long)total) + " inflated bytes (and " + std::to_string((long long)comp_len) +
+              " compressed) do not fit the free device memory: " + e.msg);
+  }
+  SNF_HIP(hipMemset(z->d_stream + total, 0, 64));
+  for (hipEvent_t& e : z->ev) if (!e) SNF_HIP(hipEventCreate(&e));
+  // ---- inflate
+  BgzfView bv{d_comp, d_mem, n_mem, z->d_stream, d_status};
+  SNF_HIP(hipEventRecord(z->ev[0], 0));
+  if (n_mem) {
+    if (k.thread_form) hipLaunchKernelGGL(bgzf_inflate_thread, dim3((unsigned)((n_mem + 63) / 64)), dim3(64), 0, 0, bv, n_mem);
+    else hipLaunchKernelGGL(bgzf_inflate_wave, dim3((unsigned)std::min<int64_t>(n_mem, k.grid_cap)), dim3(64), 0, 0, bv, n_mem);
+  }
+  SNF_HIP(hipEventRecord(z->ev[1], 0));
+  std::vector<uint32_t> status((size_t)n_mem);
+  x_d2h(status.data(), d_status, (size_t)n_mem * 4);
+  for (int64_t m = 0; m < n_mem; m++)
+    if (status[(size_t)m]) snf::fail("BGZF member " + std::to_string(m) + ": " + BZ_TEXT[status[(size_t)m] < 8 ? status[(size_t)m] : 4]);
+  // ---- record chain
+  const unsigned long long none = ~0ull;
+  unsigned long long* d_err = d_carry + 2 * (size_t)n_mem + 2;
+  SNF_HIP(hipMemset(d_carry, 0, (2 * (size_t)n_mem + 4) * 8));
+  SNF_HIP(hipMemset(d_misc, 0, 16));
+  {
+    const unsigned long long c0[2] = {BC_VALID | (unsigned long long)cin->skip << 26 |
+                                      ((unsigned long long)cin->part[0] | (unsigned long long)cin->part[1] << 8 | (unsigned long long)cin->part[2] << 16) << 2 | cin->n_part,
+                                      BC_VALID | (unsigned long long)cin->count};
+    x_h2d(d_carry, c0, 16); x_h2d(d_err, &none, 8);
+  }
+  ChainView cv{z->d_stream, d_mem, n_mem, z->d_rec_off, rec_cap - 1, d_carry, d_misc, d_err, cin->stream_pos, cin->origin, cin->count, 1u << 22};
+  SNF_HIP(hipEventRecord(z->ev[2], 0));
+  if (n_mem) hipLaunchKernelGGL(bam_chain, dim3((unsigned)n_mem), dim3(64), 0, 0, cv, n_mem);
+  SNF_HIP(hipEventRecord(z->ev[3], 0));
+  unsigned long long cout[4] = {0, 0, 0, 0};
+  x_d2h(cout, d_carry + 2 * (size_t)n_mem, 24);
+  if (cout[2] != none) {
+    const int code = (int)(cout[2] & 15);
+    if (code == BC_BLOCK_SIZE) snf::fail("truncated BAM record at byte " + std::to_string((long long)(cout[2] >> 4)));
+    snf::fail(code == BC_TIMEOUT ? "record chain: a segment's predecessor never published its carry (segment at byte " + std::to_string((long long)(cout[2] >> 4)) + ")"
+                                 : "record chain: more records than the offset table holds");
+  }
+  snf_bgzf_result_t& r = z->res;
+  r = snf_bgzf_result_t{};
+  r.carry.skip = (int64_t)((cout[0] & ~BC_VALID) >> 26);
+  r.carry.n_part = (uint8_t)(cout[0] & 3); for (int b = 0; b < 3; b++) r.carry.part[b] = (uint8_t)(cout[0] >> (2 + 8 * b));
+  r.carry.count = (int64_t)(cout[1] & ~(BC_VALID | BC_ABORT));
+  r.carry.stream_pos = cin->stream_pos + total; r.carry.origin = cin->origin;
+  const int64_t n = r.carry.count - cin->count;
+  const int64_t end = cin->stream_pos + total - cin->origin;
+  x_h2d(z->d_rec_off + n, &end, 8);
+  // ---- heads, then the names at the width the heads give
+  z->h_rec_off.assign((size_t)n + 1, 0); z->h_heads.assign((size_t)n * 6 + 1, 0);
+  x_d2h(z->h_rec_off.data(), z->d_rec_off, ((size_t)n + 1) * 8);
+  uint32_t width = 0;
+  if (n) {
+    uint32_t* d_heads = x_alloc<uint32_t>(z->dev, (size_t)n * 6);
+    HeadsView hv{z->d_stream, total, z->d_rec_off, cin->origin - cin->stream_pos, d_heads, nullptr, d_misc + 1, 0, 0};
+    hipLaunchKernelGGL(bam_heads, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, hv, n);
+    x_d2h(&width, d_misc + 1, 4);
+    x_d2h(z->h_heads.data(), d_heads, (size_t)n * 24);
+    z->h_names.assign((size_t)n * width + 1, 0);
+    if (width) {
+      hv.names = x_alloc<uint8_t>(z->dev, (size_t)n * width); hv.width = (int32_t)width; hv.phase = 1;
+      hipLaunchKernelGGL(bam_heads, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, hv, n);
+      x_d2h(z->h_names.data(), hv.names, (size_t)n * width);
+    }
+  } else z->h_names.assign(1, 0);
+  SNF_HIP(hipDeviceSynchronize());
+  SNF_HIP(hipEventElapsedTime(&r.ms_inflate, z->ev[0], z->ev[1])); SNF_HIP(hipEventElapsedTime(&r.ms_chain, z->ev[2], z->ev[3]));
+  r.stream_len = total; r.n_records = n; r.rec_off = z->h_rec_off.data(); r.heads = z->h_heads.data(); r.names = z->h_names.data();
+  r.name_width = (int32_t)width; r.device = z->device; r.d_stream = z->d_stream; r.d_rec_off = z->d_rec_off;
+  z->have = true;
+}
+}  // namespace
+
+#define Z_TRY(stmt)                                                    \
+  try { stmt; }                                                        \
+  catch (const snf::Error& e) { g_zerr = e.msg; return 1; }            \
+  catch (const std::exception& e) { g_zerr = e.what(); return 1; }     \
+  return 0;
+
+extern "C" {
+const char* snf_bgzf_last_error(void) { return g_zerr.c_str(); }
+int snf_bgzf_create(int device, snf_bgzf_t** out) {
+  if (!out) { g_zerr = "snf_bgzf_create: null argument"; return 1; }
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { g_zerr = "no HIP device: the BGZF kernels need a gfx950 GPU (there is no CPU fallback)"; return 1; }
+  if (device < 0 || device >= nd) { g_zerr = "device index out of range"; return 1; }
+  if (hipSetDevice(device) != hipSuccess) { g_zerr = "hipSetDevice failed"; return 1; }
+  snf_bgzf* z = new snf_bgzf();
+  z->device = device;
+  *out = z;
+  return 0;
+}
+int snf_bgzf_inflate(snf_bgzf_t* z, const uint8_t* compressed, int64_t compressed_len, const snf_bgzf_member_t* members, int64_t n_members,
+                     const snf_bam_carry_t* carry_in) {
+  if (!z) { g_zerr = "null handle"; return 1; }
+  if (hipSetDevice(z->device) != hipSuccess) { g_zerr = "hipSetDevice failed"; return 1; }
+  Z_TRY(do_bgzf_inflate(z, compressed, compressed_len, members, n_members, carry_in))
+}
+int snf_bgzf_result(snf_bgzf_t* z, snf_bgzf_result_t* out) {
+  if (!z || !out) { g_zerr = "null argument"; return 1; }
+  if (!z->have) { g_zerr = "snf_bgzf_result before a successful snf_bgzf_inflate"; return 1; }
+  *out = z->res;
+  return 0;
+}
+int snf_bgzf_read_stream(snf_bgzf_t* z, int64_t off, int64_t len, uint8_t* dst) {
+  if (!z || (len && !dst)) { g_zerr = "null argument"; return 1; }
+  if (!z->have) { g_zerr = "snf_bgzf_read_stream before a successful snf_bgzf_inflate"; return 1; }
+  if (off < 0 || len < 0 || off + len > z->res.stream_len) { g_zerr = "snf_bgzf_read_stream: range outside the stream"; return 1; }
+  if (hipSetDevice(z->device) != hipSuccess) { g_zerr = "hipSetDevice failed"; return 1; }
+  Z_TRY(x_d2h(dst, z->d_stream + off, (size_t)len))
+}
+void snf_bgzf_destroy(snf_bgzf_t* z) {
+  if (!z) return;
+  x_release(z->dev);
+  for (hipEvent_t e : z->ev) if (e) (void)hipEventDestroy(e);
+  delete z;
 }
 }

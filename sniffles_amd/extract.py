@@ -59,6 +59,21 @@ class Extractor:
         rank, names = qranks if qranks is not None else bam.qname_ranks(recs)
         hashes, hrank, rank_of_refid, contig_names = bam.contig_tables(recs.ref_names)
         rid = recs.ref_names.index(contig)
+        if isinstance(recs, bam.DeviceBamRecords):
+            # blob and offsets are in HBM already (bam.read_bam_device): attached, not copied; the checks come from the heads
+            rank = np.ascontiguousarray(rank, np.uint32)
+            heads = np.ascontiguousarray(recs.heads, np.uint32)
+            inp = abi.snf_extract_input_t(
+                records=C.cast(C.c_void_p(recs.d_blob), abi.u8p), records_len=int(recs.blob_len),
+                rec_off=C.cast(C.c_void_p(recs.d_rec_off), C.POINTER(C.c_int64)), n_records=recs.n,
+                qname_rank=rank.ctypes.data_as(C.POINTER(C.c_uint32)), region_ref_id=rid,
+                region_rank=int(rank_of_refid[rid]), region_start=int(start), region_end=int(end),
+                read_id_offset=int(read_id_offset), n_contigs=len(recs.ref_names),
+                contig_hash=hashes.ctypes.data_as(C.POINTER(C.c_uint64)), contig_rank=hrank.ctypes.data_as(C.POINTER(C.c_int32)))
+            self._keep = (recs.handle, heads, rank, hashes, hrank)      # (the snf_bgzf_t outlives the extraction)
+            self._check(self.lib.snf_extract_attach_device(self._h, C.byref(inp), heads.ctypes.data_as(C.POINTER(C.c_uint32)), int(recs.device)))
+            self._ctx = dict(contig=contig, contig_len=int(recs.ref_lens[rid]), qnames=names, contig_names=contig_names)
+            return
         blob = np.ascontiguousarray(recs.blob, np.uint8)
         off = np.ascontiguousarray(recs.rec_off, np.int64)
         rank = np.ascontiguousarray(rank, np.uint32)

@@ -91,6 +91,16 @@ def bind(lib: C.CDLL) -> C.CDLL:
     for f in ("snf_extract_create", "snf_extract_upload", "snf_extract_run", "snf_extract_result", "snf_extract_result_meta",
               "snf_extract_device_view", "snf_batch_add_task_device"):
         getattr(lib, f).restype = C.c_int
+    lib.snf_extract_attach_device.argtypes = [vp, C.POINTER(abi.snf_extract_input_t), C.POINTER(C.c_uint32), C.c_int]
+    lib.snf_bgzf_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.snf_bgzf_inflate.argtypes = [vp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(abi.snf_bam_carry_t)]
+    lib.snf_bgzf_result.argtypes = [vp, C.POINTER(abi.snf_bgzf_result_t)]
+    lib.snf_bgzf_read_stream.argtypes = [vp, C.c_int64, C.c_int64, C.c_void_p]
+    lib.snf_bgzf_destroy.argtypes = [vp]
+    lib.snf_bgzf_destroy.restype = None
+    lib.snf_bgzf_last_error.restype = C.c_char_p
+    for f in ("snf_extract_attach_device", "snf_bgzf_create", "snf_bgzf_inflate", "snf_bgzf_result", "snf_bgzf_read_stream"):
+        getattr(lib, f).restype = C.c_int
     lib.snf_batch_pass.argtypes = [vp]
     lib.snf_batch_open.argtypes = [C.POINTER(abi.snf_config_t), C.c_int, C.POINTER(abi.snf_task_input_t), C.c_int32, C.c_int, C.POINTER(vp)]
     for f in ("snf_batch_open", "snf_batch_pass", "snf_batch_create", "snf_batch_add_task", "snf_batch_upload", "snf_batch_call_candidates",

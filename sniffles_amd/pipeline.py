@@ -138,7 +138,10 @@ def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None,
     `reference` / `config.reference`: the reference FASTA (see `open_reference`) - with it the coverage of every task is masked
     where the reference base is 'N' (`_mask_N_coverage`, leadprov.py:420-443, 470) and the writer resolves REF / ALT."""
     import struct
-    flags = [struct.unpack_from("<H", records.blob, int(o) + 18)[0] for o in records.rec_off[:-1]]
+    if isinstance(records, bam.DeviceBamRecords):      # (bam.read_bam_device: the blob is in HBM, the flags came back with the heads)
+        flags = records.flags.tolist()
+    else:
+        flags = [struct.unpack_from("<H", records.blob, int(o) + 18)[0] for o in records.rec_off[:-1]]
     total_mapped = sum(1 for f, r in zip(flags, records.ref_id.tolist()) if r >= 0 and not f & 0x4)
     config.task_read_id_offset_mult = 10 ** 9 if total_mapped == 0 else 10 ** math.ceil(math.log(total_mapped) + 1)
     config.snf = snf_path
@@ -287,7 +290,10 @@ def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle,
     by_contig = {}
     for target in reader.read_svs_iter():
         by_contig.setdefault(target.contig, []).append(target)
-    flags = [struct.unpack_from("<H", records.blob, int(o) + 18)[0] for o in records.rec_off[:-1]]
+    if isinstance(records, bam.DeviceBamRecords):
+        flags = records.flags.tolist()
+    else:
+        flags = [struct.unpack_from("<H", records.blob, int(o) + 18)[0] for o in records.rec_off[:-1]]
     total_mapped = sum(1 for f, r in zip(flags, records.ref_id.tolist()) if r >= 0 and not f & 0x4)
     config.task_read_id_offset_mult = 10 ** 9 if total_mapped == 0 else 10 ** math.ceil(math.log(total_mapped) + 1)
     contig_lengths = [(c, int(n)) for c, n in zip(records.ref_names, records.ref_lens) if should_process_contig(c, int(n), config)]
