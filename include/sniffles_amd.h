@@ -776,6 +776,54 @@ int snf_bgzf_read_stream(snf_bgzf_t* z, int64_t off, int64_t len, uint8_t* dst);
 void snf_bgzf_destroy(snf_bgzf_t* z);
 const char* snf_bgzf_last_error(void);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * A BAM index from the run an snf_bgzf_t holds after snf_bgzf_inflate (csrc/snf_bamindex.h): per record its end
+ * (bam_endpos), its bin (reg2bin, min_shift 14 / depth 5), the virtual offsets of its first byte and of the byte behind it;
+ * the 16-kb windows the mapped records touch with the smallest start offset each; the chunks (a record opens one when its
+ * (refID, bin) differs from its predecessor's), sorted by refID << 32 | bin, file order inside a bin.  A file goes through
+ * in runs of members: the carry holds the last record of the run before.  A record the end of the run cuts (the inflate's
+ * carry.skip != 0) is left out: the caller starts the next run at the member that holds its first byte.
+ * Additive to ABI version 5.
+ */
+typedef struct snf_bai_carry {
+  int64_t count;            /* records indexed before this run (record numbers in messages count from the file's first) */
+  int32_t have_prev;        /* 0: the run starts the file */
+  int32_t prev_ref, prev_pos;
+  uint32_t prev_bin;
+  int32_t n_ref;            /* references of the BAM header; a refID outside [-1, n_ref) is refused */
+  int32_t _pad;
+  const int64_t* win_off;   /* host, n_ref + 1: the first 16-kb window of every reference in one table (the same for every run) */
+} snf_bai_carry_t;
+
+typedef struct snf_bai_run_result {
+  int64_t n_records;        /* records indexed: those of the inflate, less the one its end cuts */
+  const int64_t* end;       /* host, n_records each: bam_endpos */
+  const uint32_t* bin;
+  const uint64_t* vbeg;     /* member file offset << 16 | offset inside the member, of the record's first byte */
+  const uint64_t* vend;     /* ... of the byte behind the record (at a member border: the next non-empty member << 16) */
+  int64_t n_runs;           /* chunks opened in this run */
+  const uint64_t* runs;     /* host, n_runs x 3: refID << 32 | bin, beg, end - sorted by the key, file order inside a key */
+  int64_t head_n;           /* leading records that continue the chunk the run before ended with (same refID and bin) */
+  uint64_t head_end;        /* ... and the end of the last of them */
+  int64_t n_windows;        /* windows touched */
+  const int64_t* win_index; /* host: index into the window table (win_off[refID] + (pos >> 14)), ascending */
+  const uint64_t* win_min;  /* host: the smallest vbeg of the mapped records that overlap the window */
+  int32_t status;           /* 0 */
+  int32_t _pad;
+  snf_bai_carry_t carry;    /* what the next run starts from; win_off comes back NULL (it is the caller's table): set it again */
+  float ms_span, ms_linear, ms_runs;   /* device times (HIP events around the launches only, no copy to the host inside): bai_span; bai_linear;
+                                          ms_runs = flag + scan, plus compact + sort + table (the chunk count goes to the host between the two) */
+  float _pad2;
+} snf_bai_run_result_t;
+
+/* `member_file_off`: host, n_members + 1 of the last snf_bgzf_inflate - the file offset of every member and of the byte behind
+ * the last.  Refusals (the handle stays usable): "truncated BAM record at byte <stream position>" for a record whose n_cigar_op /
+ * l_read_name reach past its block_size; "BAM not coordinate-sorted: record <number> ..." for a position that decreases inside a
+ * reference, a reference that decreases, a placed record behind an unplaced one - always the first such record in file order.
+ * The result is library-owned until the next snf_bai_run / snf_bgzf_inflate / destroy. */
+int snf_bai_run(snf_bgzf_t* z, const int64_t* member_file_off, const snf_bai_carry_t* in, snf_bai_run_result_t* out);
+const char* snf_bai_last_error(void);
+
 /* snf_extract_upload for a blob and a record table that are in HBM already (an snf_bgzf_t's, which must outlive the use):
  * in->records and in->rec_off are DEVICE pointers on `device` - rec_off may point into the middle of the file's table, its
  * offsets are relative to in->records; in->qname_rank and the contig tables are host pointers.  `heads`: host, n_records x 6 as

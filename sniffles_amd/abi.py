@@ -450,6 +450,20 @@ class snf_bgzf_result_t(C.Structure):
                 ("d_rec_off", C.c_void_p), ("ms_inflate", C.c_float), ("ms_chain", C.c_float)]
 
 
+# ---- BAM index of a run (snf_bai_run, csrc/snf_bamindex.h)
+class snf_bai_carry_t(C.Structure):
+    _fields_ = [("count", i64), ("have_prev", i32), ("prev_ref", i32), ("prev_pos", i32), ("prev_bin", C.c_uint32), ("n_ref", i32),
+                ("_pad", i32), ("win_off", C.POINTER(C.c_int64))]
+
+
+class snf_bai_run_result_t(C.Structure):
+    _fields_ = [("n_records", i64), ("end", C.POINTER(C.c_int64)), ("bin", C.POINTER(C.c_uint32)), ("vbeg", C.POINTER(C.c_uint64)),
+                ("vend", C.POINTER(C.c_uint64)), ("n_runs", i64), ("runs", C.POINTER(C.c_uint64)), ("head_n", i64),
+                ("head_end", C.c_uint64), ("n_windows", i64), ("win_index", C.POINTER(C.c_int64)), ("win_min", C.POINTER(C.c_uint64)),
+                ("status", i32), ("_pad", i32), ("carry", snf_bai_carry_t), ("ms_span", C.c_float), ("ms_linear", C.c_float),
+                ("ms_runs", C.c_float), ("_pad2", C.c_float)]
+
+
 def extract_config_struct(cfg) -> snf_extract_config_t:
     """`cfg`: anything with the SnifflesConfig attribute names extraction reads (config.py:190-215, 507-617)."""
     g = lambda name, default: getattr(cfg, name, default)

@@ -160,6 +160,8 @@ def contig_records(recs: BamRecords, contig: str) -> BamRecords:
     """The mapped records of one contig in file order (what `bam.fetch(contig)` iterates).  A region fetch
     additionally drops records that do not overlap the region; the kernel applies the reference's own
     `reference_start` window (leadprov.py:500), which is the stricter test, so contig granularity is enough."""
+    if isinstance(recs, IndexedBam):
+        return recs.fetch_device(contig)
     if isinstance(recs, DeviceBamRecords):
         return recs.contig_view(contig)
     rid = recs.ref_names.index(contig)
@@ -211,13 +213,16 @@ def qname_ranks(recs: BamRecords):
 
 
 # ---------------------------------------------------------------------------------- the same container layer on the device
-def bgzf_members(data: bytes) -> np.ndarray:
+def bgzf_members(data: bytes, start: int = 0, stop: int = None, max_bytes: int = None) -> np.ndarray:
     """The host-side hop over the member headers (BSIZE): one row per BGZF member - offset and length of its deflate payload,
     ISIZE and the offset of its output (the exclusive sum of ISIZE) - `abi.BGZF_MEMBER_DTYPE`, what `snf_bgzf_inflate` takes.
-    Raises what `bgzf_inflate` raises for a bad magic or a missing BC field."""
+    Raises what `bgzf_inflate` raises for a bad magic or a missing BC field.
+    `start` / `stop`: only the members that begin in [start, stop) of `data` (a memory-mapped file is touched there only);
+    `max_bytes`: at least one member, then as many as stay within that many compressed bytes - and the empty members that follow
+    them (the virtual offset of a record that ends at a member border names the next member that holds a byte)."""
     from .abi import BGZF_MEMBER_DTYPE
     rows = []
-    p, n, out = 0, len(data), 0
+    p, n, out = int(start), len(data) if stop is None else min(int(stop), len(data)), 0
     while p < n:
         if data[p:p + 4] != b"\x1f\x8b\x08\x04":
             raise ValueError(f"not a BGZF block at byte {p}")
@@ -231,9 +236,11 @@ def bgzf_members(data: bytes) -> np.ndarray:
             q += 4 + slen
         if bsize is None:
             raise ValueError("BGZF block without BC field")
-        if p + bsize > n or bsize < 12 + xlen + 8:
+        if p + bsize > len(data) or bsize < 12 + xlen + 8:
             raise ValueError(f"truncated BGZF block at byte {p}")
         isize = struct.unpack_from("<I", data, p + bsize - 4)[0]
+        if max_bytes is not None and rows and isize and p + bsize - int(start) > max_bytes:
+            break
         rows.append((p + 12 + xlen, out, bsize - 8 - 12 - xlen, isize))
         out += isize
         p += bsize
@@ -304,6 +311,32 @@ class BgzfDevice:
                     carry=out_carry, d_stream=int(r.d_stream or 0), d_rec_off=int(r.d_rec_off or 0), device=int(r.device),
                     ms_inflate=float(r.ms_inflate), ms_chain=float(r.ms_chain))
 
+    def bai_run(self, member_file_off: np.ndarray, win_off: np.ndarray, carry=None) -> dict:
+        """The index tables of the run the last `inflate` left in HBM (csrc/snf_bamindex.h).  `member_file_off`: n_members + 1
+        (`member_file_offsets`); `win_off`: the first 16-kb window of every reference in one table, n_ref + 1; `carry`: the
+        `snf_bai_carry_t` the run before returned, or None at the start of the file."""
+        import ctypes as C
+        from . import abi
+        foff = np.ascontiguousarray(member_file_off, np.int64)
+        wo = np.ascontiguousarray(win_off, np.int64)
+        cin = abi.snf_bai_carry_t() if carry is None else abi.snf_bai_carry_t.from_buffer_copy(carry)
+        cin.n_ref = int(wo.shape[0] - 1)
+        cin.win_off = wo.ctypes.data_as(C.POINTER(C.c_int64))
+        r = abi.snf_bai_run_result_t()
+        if self.lib.snf_bai_run(self._h, foff.ctypes.data, C.byref(cin), C.byref(r)) != 0:
+            msg = self.lib.snf_bai_last_error().decode("utf-8", "replace")
+            if msg.startswith(("truncated BAM record", "BAM not coordinate-sorted")):
+                raise ValueError(msg)
+            raise self._err(msg)
+        n, k, w = int(r.n_records), int(r.n_runs), int(r.n_windows)
+        col = lambda ptr, cnt, dt: np.ctypeslib.as_array(ptr, shape=(cnt,)).copy() if cnt else np.zeros(0, dt)
+        out_carry = abi.snf_bai_carry_t.from_buffer_copy(r.carry)
+        out_carry.win_off = None
+        return dict(n=n, end=col(r.end, n, np.int64), bin=col(r.bin, n, np.uint32), vbeg=col(r.vbeg, n, np.uint64), vend=col(r.vend, n, np.uint64),
+                    runs=col(r.runs, 3 * k, np.uint64).reshape(k, 3), head_n=int(r.head_n), head_end=int(r.head_end),
+                    win_index=col(r.win_index, w, np.int64), win_min=col(r.win_min, w, np.uint64), carry=out_carry,
+                    ms_span=float(r.ms_span), ms_linear=float(r.ms_linear), ms_runs=float(r.ms_runs))
+
     def read_stream(self, off: int, length: int) -> bytes:
         """Inflated bytes of the last run, copied back to the host (tests)."""
         out = np.zeros(max(1, int(length)), np.uint8)
@@ -341,6 +374,7 @@ class DeviceBamRecords:
     device: int
     keep: np.ndarray = None  # contig view: the records `contig_records` keeps on the host (mapped, of the contig)
     info: dict = None        # read_bam_device: kernel times and byte counts
+    owns_handle: bool = False  # `IndexedBam.fetch_device`: these records are all their handle holds, `close` frees it
 
     @property
     def n(self) -> int:
@@ -348,6 +382,12 @@ class DeviceBamRecords:
 
     def qname(self, i: int) -> str:
         return self.names[i].tobytes().split(b"\0", 1)[0].decode("ascii")
+
+    def close(self):
+        """Free the device memory behind the records, if they own it (`IndexedBam.fetch_device`).  A table of `read_bam_device`
+        and its contig views share one handle, which stays with whoever loaded the file (`recs.handle.close()`): nothing happens."""
+        if self.owns_handle:
+            self.handle.close()
 
     def qname_ranks(self):
         """`qname_ranks` over the name table (records a contig view does not keep get rank 0: the extraction skips them)."""
@@ -390,20 +430,34 @@ def read_bam_device(path: str, device: int = 0) -> DeviceBamRecords:
     return bam_device(data, device)
 
 
-def bam_device(data: bytes, device: int = 0) -> DeviceBamRecords:
-    members = bgzf_members(data)
-    raw, hdr = b"", None
-    for m in members:
+def member_file_offsets(members: np.ndarray, start: int = 0) -> np.ndarray:
+    """int64[n + 1]: the file offset of every member of a `bgzf_members` table that begins at `start`, and of the byte behind the last."""
+    off = np.empty(members.shape[0] + 1, np.int64)
+    off[0] = int(start)
+    off[1:] = members["payload_off"] + members["payload_len"].astype(np.int64) + 8
+    return off
+
+
+def leading_header(data):
+    """(ref_names, ref_lens, header length) of a BGZF-compressed BAM: zlib over the leading members only (`data` may be a memory map)."""
+    raw, hdr, p = b"", None, 0
+    while hdr is None and p < len(data):
+        m = bgzf_members(data, p, p + 1)[0]
         a, ln = int(m["payload_off"]), int(m["payload_len"])
         part = zlib.decompress(data[a:a + ln], -15) if m["isize"] else b""
         if len(part) != int(m["isize"]):
             raise ValueError("BGZF block size mismatch")
         raw += part
         hdr = _bam_header(raw)
-        if hdr is not None:
-            break
+        p = a + ln + 8
     if hdr is None:
         raise ValueError("not a BAM stream")
+    return hdr
+
+
+def bam_device(data: bytes, device: int = 0) -> DeviceBamRecords:
+    members = bgzf_members(data)
+    hdr = leading_header(data)
     names, lens, hlen = hdr
     z = BgzfDevice(device)
     try:
@@ -426,3 +480,242 @@ def bam_device(data: bytes, device: int = 0) -> DeviceBamRecords:
     return DeviceBamRecords(names, lens, r["rec_off"], heads[:, 1].astype(np.uint32).view(np.int32).copy(),
                             heads[:, 2].astype(np.uint32).view(np.int32).copy(), (heads[:, 4] >> 16).astype(np.uint16), heads, r["names"], z,
                             r["d_stream"] + hlen, r["stream_len"] - hlen, r["d_rec_off"], r["device"], info=info)
+
+
+# ------------------------------------------------------------------------------------------------- indexed access
+def window_offsets(ref_lens) -> np.ndarray:
+    """int64[n_ref + 1]: the first 16-kb window of every reference in one table (a reference of no bases has one window)."""
+    off = np.zeros(len(ref_lens) + 1, np.int64)
+    np.cumsum([((max(int(n), 1) - 1) >> 14) + 1 for n in ref_lens], out=off[1:])
+    return off
+
+
+def _map_file(path: str):
+    import mmap
+    import os
+    if os.path.getsize(path) == 0:
+        raise ValueError("not a BAM stream")
+    with open(path, "rb") as f:
+        return mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+
+
+class _IndexTables:
+    """What the runs of `index_bam` add up to: chunks per (reference, bin) in file order, the window minima, the counts."""
+
+    def __init__(self, ref_lens):
+        from . import bamindex
+        self.ref_lens = [int(x) for x in ref_lens]
+        n_ref = len(self.ref_lens)
+        self.win_off = window_offsets(self.ref_lens)
+        self.lin = np.full(int(self.win_off[-1]), bamindex.U64_MAX, np.uint64)
+        self.chunks = {}
+        self.mapped, self.unmapped = np.zeros(n_ref, np.int64), np.zeros(n_ref, np.int64)
+        self.off_beg, self.off_end = [None] * n_ref, [None] * n_ref
+        self.n_no_coor = 0
+        self.last_key = None      # (reference, bin) of the last placed record so far: the chunk a run's leading records may continue
+
+    def add_run(self, b: dict, heads: np.ndarray):
+        """`b`: what `BgzfDevice.bai_run` returned; `heads`: the heads of the records it indexed."""
+        n_ref = len(self.ref_lens)
+        if b["head_n"] and self.last_key is not None:
+            self.chunks[self.last_key][-1][1] = b["head_end"]
+        for key, beg, end in b["runs"].tolist():
+            self.chunks.setdefault((key >> 32, key & 0xffffffff), []).append([beg, end])
+        if b["win_index"].shape[0]:
+            self.lin[b["win_index"]] = np.minimum(self.lin[b["win_index"]], b["win_min"])
+        ref = heads[:, 1].astype(np.uint32).view(np.int32)
+        placed = ref >= 0
+        is_un = ((heads[:, 4] >> 16) & 0x4) != 0
+        self.n_no_coor += int((~placed).sum())
+        if placed.any():
+            self.mapped += np.bincount(ref[placed & ~is_un], minlength=n_ref)[:n_ref]
+            self.unmapped += np.bincount(ref[placed & is_un], minlength=n_ref)[:n_ref]
+            pi = np.nonzero(placed)[0]
+            change = ref[pi][1:] != ref[pi][:-1]
+            for i in pi[np.r_[True, change]].tolist():      # the first record of every reference in this run
+                if self.off_beg[int(ref[i])] is None:
+                    self.off_beg[int(ref[i])] = int(b["vbeg"][i])
+            for i in pi[np.r_[change, True]].tolist():      # ... and the last
+                self.off_end[int(ref[i])] = int(b["vend"][i])
+        c = b["carry"]
+        self.last_key = (int(c.prev_ref), int(c.prev_bin)) if c.have_prev and c.prev_ref >= 0 else None
+
+    def finish(self):
+        from . import bamindex
+        refs = []
+        for i in range(len(self.ref_lens)):
+            seg = self.lin[int(self.win_off[i]):int(self.win_off[i + 1])]
+            known = np.nonzero(seg != np.uint64(bamindex.U64_MAX))[0]
+            seg = bamindex.fill_linear(seg[:int(known[-1]) + 1]) if known.shape[0] else np.zeros(0, np.uint64)
+            bins = {bn: np.array(ch, np.uint64).reshape(-1, 2) for (rf, bn), ch in self.chunks.items() if rf == i}
+            meta = (self.off_beg[i], self.off_end[i], int(self.mapped[i]), int(self.unmapped[i])) if self.off_beg[i] is not None else None
+            refs.append(bamindex.RefIndex(bins=bins, linear=seg, meta=meta))
+        return bamindex.BamIndex(refs, self.n_no_coor, "bai", ref_lens=self.ref_lens)
+
+
+def _next_run(r: dict, n_use: int, members: np.ndarray, foff: np.ndarray, carry, count: int):
+    """Where the run behind this one starts: (file offset, chain carry, inflated bytes this run is done with).  `r`: the inflate's
+    result for `members` (file offsets `foff`), of whose records the first `n_use` are whole; `carry`: what the run started from.
+    A run that ends on a record border is followed by the next member; one that cuts a record - inside its data (carry.skip) or
+    inside its block_size field (carry.n_part) - by the member that holds the record's first byte, `skip` = its offset in there."""
+    from . import abi
+    c, origin = r["carry"], int(carry.origin)
+    if not (c.skip or c.n_part):
+        return int(foff[-1]), abi.snf_bam_carry_t(skip=0, count=count, stream_pos=int(c.stream_pos), origin=origin, n_part=0), r["stream_len"]
+    p = (int(r["rec_off"][n_use]) + origin - int(carry.stream_pos)) if c.skip else r["stream_len"] - int(c.n_part)      # in this run's stream
+    m = int(np.searchsorted(members["out_off"], p, side="right")) - 1                                               # (never an empty member)
+    at = int(members["out_off"][m])
+    return int(foff[m]), abi.snf_bam_carry_t(skip=p - at, count=count, stream_pos=int(carry.stream_pos) + at, origin=origin, n_part=0), at
+
+
+def index_bam(path: str, out: str = None, device: int = 0, run_bytes: int = 256 << 20, stats: dict = None):
+    """The BAI of a coordinate-sorted BAM, built on the GPU (csrc/snf_bamindex.h); written to `out` if given.  The file is
+    memory-mapped and goes through in runs of members of at most `run_bytes` compressed bytes: `BgzfDevice.inflate`, then
+    `BgzfDevice.bai_run`; the host merges the tables of the runs (`_IndexTables`).  A run usually ends inside a record: that record
+    is left out of the run and the next run starts at the member that holds its first byte (`_next_run`); a record larger than a
+    run grows the run.  Refuses what htslib refuses: a file that is not coordinate-sorted (ValueError, naming the first offending
+    record).  `stats`: filled with the number of runs, the kernel times and the byte counts."""
+    from . import abi, bamindex
+    data = _map_file(path)
+    z = None
+    try:
+        names, lens, hlen = leading_header(data)
+        size = len(data)
+        tables = _IndexTables(lens)
+        z = BgzfDevice(device)
+        fo, budget = 0, max(1, int(run_bytes))
+        carry = abi.snf_bam_carry_t(skip=hlen, count=0, stream_pos=0, origin=hlen, n_part=0)
+        bcarry = None
+        info = dict(runs=0, ms_inflate=0.0, ms_chain=0.0, ms_span=0.0, ms_linear=0.0, ms_runs=0.0, stream_bytes=0, peak_stream_len=0,
+                    bytes_h2d=0)
+        while fo < size:
+            members = bgzf_members(data, fo, max_bytes=budget)
+            foff = member_file_offsets(members, fo)
+            stop = int(foff[-1])
+            rel = members.copy()
+            rel["payload_off"] -= fo
+            try:
+                r = z.inflate(memoryview(data)[fo:stop], rel, carry=carry)
+            except z._err as e:
+                if str(e).startswith("truncated BAM record"):
+                    raise ValueError(str(e)) from None
+                raise
+            c = r["carry"]
+            cut = bool(c.skip or c.n_part)
+            if cut and stop >= size:                  # the chain does not end at the end of the stream
+                at = hlen + int(r["rec_off"][r["n"] - 1]) if c.skip else int(carry.stream_pos) + r["stream_len"] - int(c.n_part)
+                raise ValueError(f"truncated BAM record at byte {at}")
+            n_use = r["n"] - (1 if c.skip and r["n"] else 0)
+            if cut and n_use == 0:                    # not one whole record (or the header) in this run: a longer one from the same place
+                budget *= 2
+                continue
+            b = z.bai_run(foff, tables.win_off, bcarry)
+            assert b["n"] == n_use
+            tables.add_run(b, r["heads"][:n_use])
+            bcarry = b["carry"]
+            info["runs"] += 1
+            for k in ("ms_inflate", "ms_chain"):
+                info[k] += r[k]
+            for k in ("ms_span", "ms_linear", "ms_runs"):
+                info[k] += b[k]
+            info["peak_stream_len"] = max(info["peak_stream_len"], r["stream_len"])
+            info["bytes_h2d"] += stop - fo + members.nbytes + foff.nbytes
+            fo, carry, done = _next_run(r, n_use, members, foff, carry, int(bcarry.count))
+            info["stream_bytes"] += done
+            budget = max(1, int(run_bytes))
+        index = tables.finish()
+        if stats is not None:
+            stats.update(info)
+        if out is not None:
+            bamindex.write_bai(index, out)
+        return index
+    finally:
+        if z is not None:
+            z.close()
+        data.close()
+
+
+class IndexedBam:
+    """A BAM file with its index (`open_indexed`): the header, the counts of the index, and `fetch_device` - only the compressed
+    bytes a contig or a region needs are read and uploaded, the records a fetch returns own their device memory."""
+
+    def __init__(self, path, data, ref_names, ref_lens, hlen, index, device):
+        self.path, self._data, self.ref_names, self.ref_lens, self.hlen, self.index, self.device = path, data, ref_names, ref_lens, hlen, index, device
+        self.fetches = []        # the `info` of every fetch so far (bytes_read, stream_len, ...)
+
+    def close(self):
+        if self._data is not None:
+            self._data.close()
+            self._data = None
+
+    def fetch_device(self, contig: str, start: int = None, end: int = None) -> DeviceBamRecords:
+        """A superset of the records `bam.fetch(contig, start, end)` iterates, in file order, in HBM: everything that starts
+        between the first and the last chunk the index gives for the interval; `keep` marks the mapped ones of the contig (the
+        extraction applies the interval itself).  Close the returned records to free the contig."""
+        from . import abi
+        rid = self.ref_names.index(contig)
+        data = self._data
+        ch = self.index.query(rid, 0 if start is None else start, end)
+        z = BgzfDevice(self.device)
+        try:
+            if ch.shape[0] == 0:
+                fo = stop = skip = 0
+                members = bgzf_members(b"")
+                end_pos = 0
+            else:
+                vb, ve = int(ch[0, 0]), int(ch[-1, 1])
+                fo, skip = vb >> 16, vb & 0xffff
+                last = ve >> 16
+                members = bgzf_members(data, fo, min(len(data), last + (1 if ve & 0xffff else 0)))
+                foff = member_file_offsets(members, fo)
+                stop = int(foff[-1])
+                k = int(np.searchsorted(foff[:-1], last, side="left"))
+                end_pos = int(members["out_off"][k]) + (ve & 0xffff) if k < members.shape[0] else int(members["isize"].sum())
+            rel = members.copy()
+            rel["payload_off"] -= fo
+            carry = abi.snf_bam_carry_t(skip=skip, count=0, stream_pos=0, origin=skip, n_part=0)
+            try:
+                r = z.inflate(memoryview(data)[fo:stop] if stop > fo else b"", rel, carry=carry)
+            except z._err as e:
+                if str(e).startswith("truncated BAM record"):
+                    raise ValueError(str(e)) from None
+                if "do not fit the free device memory" in str(e):
+                    raise z._err(f"contig {contig}: {e}") from None
+                raise
+            n = int(np.searchsorted(r["rec_off"][:r["n"]] + skip, end_pos, side="left"))      # records that start at or behind the end: not ours
+            heads = np.ascontiguousarray(r["heads"][:n])
+            ref_id = heads[:, 1].astype(np.uint32).view(np.int32).copy()
+            flags = (heads[:, 4] >> 16).astype(np.uint16)
+            info = dict(ms_inflate=r["ms_inflate"], ms_chain=r["ms_chain"], compressed_bytes=stop - fo, bytes_read=stop - fo, stream_len=r["stream_len"],
+                        bytes_h2d=stop - fo + members.nbytes, bytes_d2h=r["rec_off"].nbytes + r["heads"].nbytes + r["names"].nbytes,
+                        contig=contig, start=start, end=end)
+            self.fetches.append(info)
+            return DeviceBamRecords(self.ref_names, self.ref_lens, r["rec_off"][:n + 1], ref_id, heads[:, 2].astype(np.uint32).view(np.int32).copy(),
+                                    flags, heads, r["names"][:n], z, r["d_stream"] + skip, r["stream_len"] - skip, r["d_rec_off"], r["device"],
+                                    keep=(ref_id == rid) & ((flags & 0x4) == 0), info=info, owns_handle=True)
+        except Exception:
+            z.close()
+            raise
+
+
+def open_indexed(path: str, index=None, device: int = 0) -> IndexedBam:
+    """`path` memory-mapped, its header parsed from the leading members, its index loaded: `index` is a `bamindex.BamIndex`, the
+    path of a BAI / CSI file, or None for `bamindex.find_index(path)`.  A file without an index is refused as the reference's
+    `check_index` refuses it (`bam.index_bam` builds one)."""
+    from . import bamindex
+    if index is None:
+        index = bamindex.find_index(path)
+        if index is None:
+            raise ValueError(f"Unable to load index for input file '{path}'. Please verify that your input file is sorted + indexed "
+                             f"and that the index .bai file is valid and in the right location.")
+    if not isinstance(index, bamindex.BamIndex):
+        index = bamindex.read_index(index)
+    data = _map_file(path)
+    try:
+        names, lens, hlen = leading_header(data)
+        if index.n_ref != len(names):
+            raise ValueError(f"the index holds {index.n_ref} references, the header of {path} {len(names)}")
+    except Exception:
+        data.close()
+        raise
+    return IndexedBam(path, data, names, lens, hlen, index, device)

@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 namespace snf {
@@ -1018,6 +1019,7 @@ SNF_HD void x_totals_body(int64_t i, const ExView& v) {
 
 }  // namespace snf
 #include "snf_bgzf.h"
+#include "snf_bamindex.h"
 using namespace snf;
 SNF_KERNEL(x_count, ExView)
 SNF_KERNEL(x_emit, ExView)
@@ -1503,10 +1505,15 @@ struct snf_bgzf {
   std::vector<int64_t> h_rec_off; std::vector<uint32_t> h_heads; std::vector<uint8_t> h_names;
   snf_bgzf_result_t res{};
   bool have = false;
+  // what snf_bai_run takes from the last inflate, and its host tables
+  const snf_bgzf_member_t* d_mem = nullptr; int64_t n_mem = 0, origin = 0, stream_pos = 0;
+  std::vector<void*> bai_dev;
+  hipEvent_t bev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // span | linear | flag + scan | compact + sort + table
+  std::vector<int64_t> b_end, b_win; std::vector<uint32_t> b_bin; std::vector<uint64_t> b_vbeg, b_vend, b_runs, b_min;
 };
 
 namespace {
-thread_local std::string g_zerr;
+thread_local std::string g_zerr, g_berr;
 
 void do_bgzf_inflate(snf_bgzf* z, const uint8_t* comp, int64_t comp_len, const snf_bgzf_member_t* mem, int64_t n_mem, const snf_bam_carry_t* cin) {
   if (comp_len < 0 || n_mem < 0 || (comp_len && !comp) || (n_mem && !mem) || !cin) snf::fail("snf_bgzf_inflate: null argument");
@@ -1520,8 +1527,8 @@ void do_bgzf_inflate(snf_bgzf* z, const uint8_t* comp, int64_t comp_len, const s
     total += b.isize;
   }
   const BgzfKnobs k;
-  x_release(z->dev);
-  z->have = false; z->d_stream = nullptr; z->d_rec_off = nullptr;
+  x_release(z->dev); x_release(z->bai_dev);
+  z->have = false; z->d_stream = nullptr; z->d_rec_off = nullptr; z->d_mem = nullptr;
   const int64_t rec_cap = total / 36 + 2;      // a record is at least 36 bytes; one more for the end of the run
   uint8_t* d_comp; snf_bgzf_member_t* d_mem; uint32_t* d_status; unsigned long long* d_carry; uint32_t* d_misc;
   try {
@@ -1604,7 +1611,125 @@ void do_bgzf_inflate(snf_bgzf* z, const uint8_t* comp, int64_t comp_len, const s
   SNF_HIP(hipEventElapsedTime(&r.ms_inflate, z->ev[0], z->ev[1])); SNF_HIP(hipEventElapsedTime(&r.ms_chain, z->ev[2], z->ev[3]));
   r.stream_len = total; r.n_records = n; r.rec_off = z->h_rec_off.data(); r.heads = z->h_heads.data(); r.names = z->h_names.data();
   r.name_width = (int32_t)width; r.device = z->device; r.d_stream = z->d_stream; r.d_rec_off = z->d_rec_off;
+  z->d_mem = d_mem; z->n_mem = n_mem; z->origin = cin->origin; z->stream_pos = cin->stream_pos;
   z->have = true;
+}
+
+// ---- BAM index of the run (snf_bamindex.h)
+void do_bai_run(snf_bgzf* z, const int64_t* foff, const snf_bai_carry_t* cin, snf_bai_run_result_t* out) {
+  if (!foff || !cin || !out) snf::fail("snf_bai_run: null argument");
+  if (!z->have) snf::fail("snf_bai_run before a successful snf_bgzf_inflate");
+  if (cin->n_ref < 0 || !cin->win_off) snf::fail("snf_bai_run: window table missing");
+  for (int32_t r = 0; r < cin->n_ref; r++) if (cin->win_off[r + 1] < cin->win_off[r] || cin->win_off[0] != 0) snf::fail("snf_bai_run: win_off is not ascending from 0");
+  for (int64_t m = 0; m < z->n_mem; m++) if (foff[m] < 0 || foff[m + 1] < foff[m] || foff[m + 1] >= (1ll << 48)) snf::fail("snf_bai_run: member file offsets malformed");
+  const BaiKnobs k;
+  x_release(z->bai_dev);
+  std::vector<void*>& pool = z->bai_dev;
+  const snf_bgzf_result_t& zr = z->res;
+  const int64_t n = zr.n_records - (zr.carry.skip != 0 && zr.n_records > 0 ? 1 : 0);      // the end of the run cuts the last record
+  const int64_t n_win = cin->win_off[cin->n_ref];
+  const size_t N1 = (size_t)n + 1;
+  BaiView v{};
+  v.stream = z->d_stream; v.stream_len = zr.stream_len; v.rec_off = z->d_rec_off; v.rel = z->origin - z->stream_pos; v.n = n;
+  v.mem = z->d_mem; v.n_mem = z->n_mem; v.foff = x_up(pool, foff, (size_t)z->n_mem + 1);
+  v.end = x_alloc<int64_t>(pool, N1); v.bin = x_alloc<uint32_t>(pool, N1); v.vbeg = x_alloc<unsigned long long>(pool, N1);
+  v.vend = x_alloc<unsigned long long>(pool, N1); v.sorted = x_alloc<uint32_t>(pool, N1);
+  v.err = x_alloc<unsigned long long>(pool, 2);
+  v.lin = x_alloc<unsigned long long>(pool, (size_t)n_win); v.win_off = x_up(pool, cin->win_off, (size_t)cin->n_ref + 1); v.n_ref = cin->n_ref;
+  v.flag = x_alloc<int64_t>(pool, N1); v.run_idx = x_alloc<int64_t>(pool, N1);
+  v.prev_ref = cin->prev_ref; v.prev_pos = cin->prev_pos; v.prev_bin = cin->prev_bin; v.have_prev = cin->have_prev;
+  const unsigned long long none[2] = {~0ull, ~0ull};
+  x_h2d(v.err, none, 16);
+  SNF_HIP(hipMemset(v.lin, 0xff, (size_t)(n_win ? n_win : 1) * 8));
+  for (hipEvent_t& e : z->bev) if (!e) SNF_HIP(hipEventCreate(&e));
+  const unsigned grid_w = (unsigned)std::min<int64_t>(n > 0 ? n : 1, k.grid_cap), grid_t = (unsigned)((n + 255) / 256);
+  // (every bracket holds launches only: the copies to the host and the host's waits lie between the brackets)
+  SNF_HIP(hipEventRecord(z->bev[0], 0));
+  if (n) {
+    if (k.thread_form) hipLaunchKernelGGL(bai_span_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
+    else hipLaunchKernelGGL(bai_span_wave, dim3(grid_w), dim3(64), 0, 0, v, n);
+    SNF_HIP(hipGetLastError());
+  }
+  SNF_HIP(hipEventRecord(z->bev[1], 0));
+  unsigned long long err[2] = {~0ull, ~0ull};
+  x_d2h(err, v.err, 16);
+  z->b_end.assign(N1, 0); z->b_bin.assign(N1, 0); z->b_vbeg.assign(N1, 0); z->b_vend.assign(N1, 0);
+  x_d2h(z->b_end.data(), v.end, (size_t)n * 8); x_d2h(z->b_bin.data(), v.bin, (size_t)n * 4);
+  x_d2h(z->b_vbeg.data(), v.vbeg, (size_t)n * 8); x_d2h(z->b_vend.data(), v.vend, (size_t)n * 8);
+  if (err[0] != ~0ull) {
+    const int64_t rec = (int64_t)(err[0] >> 4); const int code = (int)(err[0] & 15);
+    x_release(pool);
+    if (code == BI_TRUNCATED) snf::fail("truncated BAM record at byte " + std::to_string((long long)(zr.rec_off[rec] + z->origin)));
+    const uint32_t* h = zr.heads + 6 * rec;
+    const std::string at = "BAM not coordinate-sorted: record " + std::to_string((long long)(cin->count + rec)) + " (reference " +
+                           std::to_string((int32_t)h[1]) + ", position " + std::to_string((int32_t)h[2]) + ")";
+    snf::fail(at + (code == BI_POS ? " lies before its predecessor's position" : code == BI_REF ? " follows a record of a later reference"
+                    : code == BI_UNPLACED ? " follows an unplaced record" : " names a reference the header does not have"));
+  }
+  // ---- linear index
+  size_t scan_need = 0;
+  SNF_HIP(rocprim::exclusive_scan(nullptr, scan_need, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  void* scan_tmp = x_alloc<uint8_t>(pool, scan_need);
+  SNF_HIP(hipEventRecord(z->bev[2], 0));
+  if (n) {
+    if (k.thread_form) hipLaunchKernelGGL(bai_linear_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
+    else hipLaunchKernelGGL(bai_linear_wave, dim3(grid_w), dim3(64), 0, 0, v, n);
+    SNF_HIP(hipGetLastError());
+  }
+  SNF_HIP(hipEventRecord(z->bev[3], 0));
+  // ---- chunks: flag, scan | the number of chunks to the host | compact, sort, table
+  hipLaunchKernelGGL(bai_flag, dim3((unsigned)((N1 + 255) / 256)), dim3(256), 0, 0, v, (int64_t)N1);
+  SNF_HIP(hipGetLastError());
+  SNF_HIP(rocprim::exclusive_scan(scan_tmp, scan_need, (const int64_t*)v.flag, v.run_idx, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  SNF_HIP(hipEventRecord(z->bev[4], 0));
+  int64_t n_runs = 0;
+  x_d2h(&n_runs, v.run_idx + n, 8);
+  x_d2h(err, v.err, 16);
+  v.n_runs = n_runs; v.n_placed = err[1] == ~0ull ? n : (int64_t)err[1];
+  z->b_runs.assign((size_t)n_runs * 3 + 1, 0);
+  int64_t head_n = 0;
+  if (n_runs) {
+    const size_t R = (size_t)n_runs;
+    v.run_start = x_alloc<int64_t>(pool, R); v.key = x_alloc<unsigned long long>(pool, R); v.val = x_alloc<uint32_t>(pool, R);
+    unsigned long long* skey = x_alloc<unsigned long long>(pool, R); uint32_t* sval = x_alloc<uint32_t>(pool, R);
+    v.table = x_alloc<unsigned long long>(pool, 3 * R);
+    size_t need = 0;
+    SNF_HIP(rocprim::radix_sort_pairs(nullptr, need, (const unsigned long long*)v.key, skey, (const uint32_t*)v.val, sval, R, 0u, 64u, 0));
+    void* tmp = x_alloc<uint8_t>(pool, need);
+    SNF_HIP(hipEventRecord(z->bev[5], 0));
+    hipLaunchKernelGGL(bai_compact, dim3(grid_t), dim3(256), 0, 0, v, n);
+    SNF_HIP(hipGetLastError());
+    SNF_HIP(rocprim::radix_sort_pairs(tmp, need, (const unsigned long long*)v.key, skey, (const uint32_t*)v.val, sval, R, 0u, 64u, 0));
+    v.skey = skey; v.sval = sval;
+    hipLaunchKernelGGL(bai_table, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, 0, v, n_runs);
+    SNF_HIP(hipGetLastError());
+    SNF_HIP(hipEventRecord(z->bev[6], 0));
+    x_d2h(z->b_runs.data(), v.table, R * 24);
+    x_d2h(&head_n, v.run_start, 8);      // records in front of the first chunk this run opens: they continue the carry's
+  } else head_n = v.n_placed;
+  // ---- the windows touched
+  std::vector<uint64_t> lin((size_t)n_win + 1);
+  x_d2h(lin.data(), v.lin, (size_t)n_win * 8);
+  SNF_HIP(hipDeviceSynchronize());
+  z->b_win.clear(); z->b_min.clear();
+  for (int64_t w = 0; w < n_win; w++) if (lin[(size_t)w] != ~0ull) { z->b_win.push_back(w); z->b_min.push_back(lin[(size_t)w]); }
+  const int64_t n_touched = (int64_t)z->b_win.size();
+  z->b_win.push_back(0); z->b_min.push_back(0);
+  snf_bai_run_result_t r{};
+  SNF_HIP(hipEventElapsedTime(&r.ms_span, z->bev[0], z->bev[1])); SNF_HIP(hipEventElapsedTime(&r.ms_linear, z->bev[2], z->bev[3]));
+  SNF_HIP(hipEventElapsedTime(&r.ms_runs, z->bev[3], z->bev[4]));
+  if (n_runs) { float ms2 = 0; SNF_HIP(hipEventElapsedTime(&ms2, z->bev[5], z->bev[6])); r.ms_runs += ms2; }
+  r.n_records = n; r.end = z->b_end.data(); r.bin = z->b_bin.data(); r.vbeg = z->b_vbeg.data(); r.vend = z->b_vend.data();
+  r.n_runs = n_runs; r.runs = z->b_runs.data(); r.head_n = head_n; r.head_end = head_n ? z->b_vend[(size_t)head_n - 1] : 0;
+  r.n_windows = n_touched; r.win_index = z->b_win.data(); r.win_min = z->b_min.data();
+  r.carry = *cin; r.carry.count = cin->count + n;
+  r.carry.win_off = nullptr;      // (the caller's table: not handed back)
+  if (n) {
+    const uint32_t* h = zr.heads + 6 * (n - 1);
+    r.carry.have_prev = 1; r.carry.prev_ref = (int32_t)h[1]; r.carry.prev_pos = (int32_t)h[2]; r.carry.prev_bin = z->b_bin[(size_t)n - 1];
+  }
+  x_release(pool);
+  *out = r;
 }
 }  // namespace
 
@@ -1646,10 +1771,20 @@ int snf_bgzf_read_stream(snf_bgzf_t* z, int64_t off, int64_t len, uint8_t* dst) 
   if (hipSetDevice(z->device) != hipSuccess) { g_zerr = "hipSetDevice failed"; return 1; }
   Z_TRY(x_d2h(dst, z->d_stream + off, (size_t)len))
 }
+int snf_bai_run(snf_bgzf_t* z, const int64_t* member_file_off, const snf_bai_carry_t* in, snf_bai_run_result_t* out) {
+  if (!z) { g_berr = "null handle"; return 1; }
+  if (hipSetDevice(z->device) != hipSuccess) { g_berr = "hipSetDevice failed"; return 1; }
+  try { do_bai_run(z, member_file_off, in, out); }
+  catch (const snf::Error& e) { g_berr = e.msg; return 1; }
+  catch (const std::exception& e) { g_berr = e.what(); return 1; }
+  return 0;
+}
+const char* snf_bai_last_error(void) { return g_berr.c_str(); }
 void snf_bgzf_destroy(snf_bgzf_t* z) {
   if (!z) return;
-  x_release(z->dev);
+  x_release(z->dev); x_release(z->bai_dev);
   for (hipEvent_t e : z->ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : z->bev) if (e) (void)hipEventDestroy(e);
   delete z;
 }
 }

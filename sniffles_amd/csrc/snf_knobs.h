@@ -9,7 +9,7 @@
 //                 here and is resolved where the data is known.
 //   ProcessKnobs  what configures state shared by all handles of the process (pacing, pools, arenas): once per process, at the
 //                 first use of process_knobs().
-//   ExtractKnobs / BgzfKnobs / CombineKnobs   the entry points without a long-lived handle: constructed at the top of each call.
+//   ExtractKnobs / BgzfKnobs / BaiKnobs / CombineKnobs   the entry points without a long-lived handle: constructed at the top of each call.
 // The parses are not uniform on purpose - each keeps the meaning its switch always had ("set at all", "atoi != 0", clamped, a
 // string compared).  Defaults are the product path; everything else exists for tests and measurements.
 #pragma once
@@ -115,6 +115,11 @@ struct ExtractKnobs {   // read at every snf_extract_run
 struct BgzfKnobs {   // read at every snf_bgzf_inflate
   bool thread_form = env_set("SNF_BGZF_THREAD");     // SNF_BGZF_THREAD (set): a thread per BGZF member, its window in HBM (the second implementation the tests compare)
   int grid_cap = env_set("SNF_BGZF_GRID") ? env_pos("SNF_BGZF_GRID", 1) : (1 << 20);   // SNF_BGZF_GRID=n (at least 1), default 2^20: the inflate grid; beyond it a wave takes several members
+};
+
+struct BaiKnobs {   // read at every snf_bai_run
+  bool thread_form = env_set("SNF_BAI_THREAD");      // SNF_BAI_THREAD (set): a thread per record in bai_span / bai_linear (the second implementation the tests compare)
+  int grid_cap = env_set("SNF_BAI_GRID") ? env_pos("SNF_BAI_GRID", 1) : (1 << 20);   // SNF_BAI_GRID=n (at least 1), default 2^20: the grid of the wave forms; beyond it a wave takes several records
 };
 
 struct CombineKnobs {   // read at every snf_combine_resolve_batch

@@ -129,20 +129,44 @@ def _extract_regions(recs, contig, regions, config, read_id_offset, task_id, tan
     return soa.concat_tasks(parts), info, _RegionExtractor()
 
 
+def _total_mapped(records) -> int:
+    """`bam.mapped` (sniffles:298): from the index for an `IndexedBam` - the file is never scanned -, else counted over the table."""
+    import struct
+    if isinstance(records, bam.IndexedBam):
+        return records.index.mapped
+    if isinstance(records, bam.DeviceBamRecords):      # (bam.read_bam_device: the blob is in HBM, the flags came back with the heads)
+        flags = records.flags.tolist()
+    else:
+        flags = [struct.unpack_from("<H", records.blob, int(o) + 18)[0] for o in records.rec_off[:-1]]
+    return sum(1 for f, r in zip(flags, records.ref_id.tolist()) if r >= 0 and not f & 0x4)
+
+
+class _ContigInput:
+    """The records of one task's contig: a view of the whole-file table, or - for an `IndexedBam` - one fetch over the hull of the
+    task's regions that owns its device memory; one contig is resident at a time and goes when the task is through."""
+
+    def __init__(self, records, contig, regions):
+        self.owned = isinstance(records, bam.IndexedBam)
+        if self.owned and regions:
+            self.recs = records.fetch_device(contig, min(a for a, _ in regions), max(b for _, b in regions))
+        else:
+            self.recs = bam.contig_records(records, contig)
+
+    def close(self):
+        if self.owned:
+            self.recs.close()
+
+
 def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None, tandem_repeats=None, device: int = 0, objects: bool = True, reference=None) -> SampleResult:
-    """`records`: `bam.read_bam(path)`.  `tandem_repeats`: {contig: [(start, end), ...]} (already padded, util.py:121-144).
+    """`records`: `bam.read_bam(path)`, `bam.read_bam_device(path)` or `bam.open_indexed(path)` (only the contigs that are processed
+    are read, through the index, one at a time).  `tandem_repeats`: {contig: [(start, end), ...]} (already padded, util.py:121-144).
     Writes the VCF to `vcf_handle` and / or the SNF to `snf_path` (CallTask.execute switches QC filtering off for the
     candidates when an SNF is requested, parallel.py:258-263).
     `objects=False`: VCF only, formatted straight from the record table (vcf.VCF.write_records) - the same text, no `SVCall`
     objects (`SampleResult.calls` stays empty); falls back to the object path when a reference FASTA is attached.
     `reference` / `config.reference`: the reference FASTA (see `open_reference`) - with it the coverage of every task is masked
     where the reference base is 'N' (`_mask_N_coverage`, leadprov.py:420-443, 470) and the writer resolves REF / ALT."""
-    import struct
-    if isinstance(records, bam.DeviceBamRecords):      # (bam.read_bam_device: the blob is in HBM, the flags came back with the heads)
-        flags = records.flags.tolist()
-    else:
-        flags = [struct.unpack_from("<H", records.blob, int(o) + 18)[0] for o in records.rec_off[:-1]]
-    total_mapped = sum(1 for f, r in zip(flags, records.ref_id.tolist()) if r >= 0 and not f & 0x4)
+    total_mapped = _total_mapped(records)
     config.task_read_id_offset_mult = 10 ** 9 if total_mapped == 0 else 10 ** math.ceil(math.log(total_mapped) + 1)
     config.snf = snf_path
     contig_lengths = [(c, int(n)) for c, n in zip(records.ref_names, records.ref_lens) if should_process_contig(c, int(n), config)]
@@ -163,16 +187,21 @@ def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None,
                                  tandem_repeats=tr, device=device)
         # the signatures never leave HBM between the extraction and the clustering batch (snf_batch_add_task_device)
         regions = regions_of(config, contig)
-        if regions:      # --regions: the task's leads and coverage come from these intervals only (sniffles:330-341)
-            ti, info, extractor = _extract_regions(bam.contig_records(records, contig), contig, regions, config,
-                                                   (task_id * config.task_read_id_offset_mult) % 2 ** 32, task_id, tr, device)
-        else:
-            ti, info, extractor = extract.extract_region_device(bam.contig_records(records, contig), contig, task.start, task.end, config,
-                                                                read_id_offset=(task_id * config.task_read_id_offset_mult) % 2 ** 32,
-                                                                task_id=task_id, sv_id_start=0, tandem_repeats=tr, device=device)
-        config.qc_nm_threshold = config.average_regional_nm = ti.qc_nm_threshold      # iter_region's side channel
-        mask_N_coverage(ti, fasta_handle, contig, regions or [(task.start, task.end)])
-        task.lead_provider = _Extracted(ti)
+        source = _ContigInput(records, contig, regions)
+        try:
+            if regions:      # --regions: the task's leads and coverage come from these intervals only (sniffles:330-341)
+                ti, info, extractor = _extract_regions(source.recs, contig, regions, config,
+                                                       (task_id * config.task_read_id_offset_mult) % 2 ** 32, task_id, tr, device)
+            else:
+                ti, info, extractor = extract.extract_region_device(source.recs, contig, task.start, task.end, config,
+                                                                    read_id_offset=(task_id * config.task_read_id_offset_mult) % 2 ** 32,
+                                                                    task_id=task_id, sv_id_start=0, tandem_repeats=tr, device=device)
+            config.qc_nm_threshold = config.average_regional_nm = ti.qc_nm_threshold      # iter_region's side channel
+            mask_N_coverage(ti, fasta_handle, contig, regions or [(task.start, task.end)])
+            task.lead_provider = _Extracted(ti)
+        except Exception:
+            source.close()
+            raise
         if not objects and snf_out is None and writer is not None and writer.can_write_records():
             import numpy as np
             try:
@@ -184,6 +213,7 @@ def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None,
             finally:
                 task.close()
                 extractor.close()      # (backs the lazy host copies of the task input: goes after the task)
+                source.close()         # (an indexed file's contig leaves HBM with its task)
             continue
         try:
             cands = task.call_candidates(qc, config)
@@ -198,6 +228,7 @@ def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None,
         finally:
             task.close()
             extractor.close()
+            source.close()
         if writer is not None:
             out.vcf_records += sum(writer.write_call(c) for c in calls)
         out.calls[task_id] = calls
@@ -284,17 +315,12 @@ def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle,
     """Force calling (`--genotype-vcf`, sniffles:190-213, 487-560 and `GenotypeTask.execute`): the SVs of the input VCF are
     matched against this sample's candidates contig by contig and written back with the sample's genotype (contig by
     contig, input order within a contig).  Returns the number of records written."""
-    import struct
     config.mode = "genotype_vcf"
     reader = vcf.VCF(config, vcf_in_handle)
     by_contig = {}
     for target in reader.read_svs_iter():
         by_contig.setdefault(target.contig, []).append(target)
-    if isinstance(records, bam.DeviceBamRecords):
-        flags = records.flags.tolist()
-    else:
-        flags = [struct.unpack_from("<H", records.blob, int(o) + 18)[0] for o in records.rec_off[:-1]]
-    total_mapped = sum(1 for f, r in zip(flags, records.ref_id.tolist()) if r >= 0 and not f & 0x4)
+    total_mapped = _total_mapped(records)
     config.task_read_id_offset_mult = 10 ** 9 if total_mapped == 0 else 10 ** math.ceil(math.log(total_mapped) + 1)
     contig_lengths = [(c, int(n)) for c, n in zip(records.ref_names, records.ref_lens) if should_process_contig(c, int(n), config)]
     config.contig_lengths = contig_lengths
@@ -308,8 +334,12 @@ def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle,
         task = parallel.GenotypeTask(id=task_id, sv_id=0, contig=contig, start=0, end=length - 1, config=config, tandem_repeats=tr,
                                      genotype_svs=targets, device=device)
         regions = regions_of(config, contig) or [(task.start, task.end)]       # --regions: leads and coverage from these intervals only
-        ti, _, _ = _extract_regions(bam.contig_records(records, contig), contig, regions, config,
-                                    (task_id * config.task_read_id_offset_mult) % 2 ** 32, task_id, tr, device)
+        source = _ContigInput(records, contig, regions_of(config, contig))
+        try:
+            ti, _, _ = _extract_regions(source.recs, contig, regions, config,
+                                        (task_id * config.task_read_id_offset_mult) % 2 ** 32, task_id, tr, device)
+        finally:
+            source.close()      # (the task input is on the host: the contig's records are not needed any more)
         config.qc_nm_threshold = config.average_regional_nm = ti.qc_nm_threshold
         mask_N_coverage(ti, fasta_handle, contig, regions)
         task.lead_provider = _Extracted(ti)
