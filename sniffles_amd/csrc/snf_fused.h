@@ -68,6 +68,24 @@ SNF_D void tile_scan(const View& v, int slot0, const unsigned long long (&val)[K
   for (int k = 0; k < K; k++) off[k] = prefix[k] + excl[k];
 }
 
+// tile prefix for the slots whose sums the producers of the flags publish themselves (flag_publish, snf_stage_call.h: TS_REFINED,
+// TS_CALLS): there is no super-tile level, a block adds up the tiles in front of it directly (ten loads per thread at 2 600 tiles),
+// as e3b_offsets and f2k_outscan do
+template <int K>
+SNF_D void tile_scan_direct(const View& v, int slot0, const unsigned long long (&val)[K], unsigned long long (&off)[K], unsigned long long* lds) {
+  unsigned long long part[K], dummy[K], prefix[K], excl[K], tot[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    unsigned long long a = 0;
+    for (int64_t t = threadIdx.x; t < (int64_t)blockIdx.x; t += 256) a += v.tile_sums[(int64_t)(slot0 + k) * v.tile_stride + t];
+    part[k] = a;
+  }
+  block_exscan256<K>(part, dummy, prefix, lds);
+  block_exscan256<K>(val, excl, tot, lds);
+#pragma unroll
+  for (int k = 0; k < K; k++) off[k] = prefix[k] + excl[k];
+}
+
 // ---- the same chain in ONE launch: decoupled look-back.  A block takes a ticket (= its tile: tiles start in ticket order, so every
 // predecessor of a tile is running or done), scans its 256 elements, publishes the tile aggregate, sums the aggregates of the tiles
 // before it back to the nearest one whose inclusive prefix is known (64 predecessors per step, one per lane of wave 0), publishes its
@@ -156,6 +174,9 @@ __global__ void __launch_bounds__(256) z0_init(const View v, int64_t n) {
   if (i <= T + 1) v.t_call_off[i] = 0;
   if (i < G) { v.grp_first_bin[i] = -1; v.grp_seed_lo[i] = -1; v.grp_seed_hi[i] = -1; v.grp_dirty[i] = 0; }
   if (i < TS_SLOTS * v.super_stride) v.tile_super[i] = 0;
+  if (i < v.tile_stride) {      // tile sums the producers of the flags add to (flag_publish)
+    v.tile_sums[(int64_t)TS_REFINED * v.tile_stride + i] = 0; v.tile_sums[(int64_t)TS_CALLS * v.tile_stride + i] = 0;
+  }
   if (i == 0) *v.chain_epoch += 1u;                          // tags of this pass's chain launches (chain_scan)
   if (v.wave_path && i < 3 * 64 * 16) v.big_cnt[i] = 0;      // lists of the big-cluster kernels (x_big)
   if (v.wave_path && i < 3 * 64 * 16) v.d2cnt[i] = 0;       // lists of the grouped call kernels (snf_wave_call_g.h)
@@ -243,19 +264,12 @@ SNF_FUSED_HEAD(b2k_runs)
     b2_emit(p, v);
   }
 }
-// generic "count an existing flag array" + scan + emit chains: clusters (C4), refined clusters (D1b), calls (D3a)
-#define SNF_FLAGSUM(name, flag, slot)                                          \
-  SNF_FUSED_HEAD(name)                                                          \
-    unsigned long long val[1] = {p < n ? (unsigned long long)v.flag[p] : 0ull}; \
-    tile_publish<1>(v, slot, val, lds);                                         \
-  }
-SNF_FLAGSUM(c4a_count, clflag, TS_CLUSTERS)
-SNF_FLAGSUM(d1a_count, rcflag, TS_REFINED)
-// (flags behind n_rc are stale: the wave kernels only write the flags of existing refined clusters, and the thread kernel that
-// used to reset the rest is not launched next to them)
-SNF_FUSED_HEAD(d3a_count)
-  unsigned long long val[1] = {(p < n && p < v.cnt->n_rc) ? (unsigned long long)v.cdflag[p] : 0ull};
-  tile_publish<1>(v, TS_CALLS, val, lds);
+// "count an existing flag array" + scan + emit chain of the merged clusters (C4: clflag is set and cleared at several places of the
+// merge).  The flags of the refined clusters (D1b) and of the calls (D3) are counted by whoever sets them (flag_publish): their
+// chains are the emit kernel alone.
+SNF_FUSED_HEAD(c4a_count)
+  unsigned long long val[1] = {p < n ? (unsigned long long)v.clflag[p] : 0ull};
+  tile_publish<1>(v, TS_CLUSTERS, val, lds);
 }
 SNF_FUSED_HEAD(c4k_clusters)
   unsigned long long val[1] = {p < n ? (unsigned long long)v.clflag[p] : 0ull}, off[1];
@@ -268,16 +282,18 @@ SNF_FUSED_HEAD(c4k_clusters)
 }
 SNF_FUSED_HEAD(d1bk_rctable)
   unsigned long long val[1] = {p < n ? (unsigned long long)v.rcflag[p] : 0ull}, off[1];
-  tile_scan<1>(v, TS_REFINED, val, off, lds);
+  tile_scan_direct<1>(v, TS_REFINED, val, off, lds);
   if (p < n) {
     v.rcscan[p] = (uint32_t)off[0];
     if (p == n - 1) { v.rcscan[n] = (uint32_t)(off[0] + val[0]); v.cnt->n_rc = (int64_t)(off[0] + val[0]); }
     d1b_emit(p, v);
   }
 }
+// (flags behind n_rc are stale: the wave kernels only write the flags of existing refined clusters, and the thread kernel that
+// used to reset the rest is not launched next to them)
 SNF_FUSED_HEAD(d3ck_compact)
   unsigned long long val[1] = {(p < n && p < v.cnt->n_rc) ? (unsigned long long)v.cdflag[p] : 0ull}, off[1];
-  tile_scan<1>(v, TS_CALLS, val, off, lds);
+  tile_scan_direct<1>(v, TS_CALLS, val, off, lds);
   if (p < n) {
     v.cdscan[p] = (uint32_t)off[0];
     if (p == n - 1) { v.cdscan[n] = (uint32_t)(off[0] + val[0]); v.cnt->n_calls = (int64_t)(off[0] + val[0]); }

@@ -324,6 +324,7 @@ struct snf_batch_impl {
   ReadPrep rp{};
   Counts* h_cnt = nullptr;        // counters as last read back (lives in the pinned result block hb_res)
   void* sort_tmp[2] = {nullptr, nullptr}; size_t sort_tmp_bytes[2] = {0, 0};  // rocPRIM temp storage per stream
+  hipEvent_t ev_cls_fork = nullptr, ev_cls_join = nullptr;   // grouped kernel of a refine / call stage beside its partner (ClassFork)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork3 = nullptr, ev_join3 = nullptr, ev_base = nullptr,
              ev_counts = nullptr, ev_rn = nullptr, ev_join4 = nullptr, ev_e3 = nullptr;  // host waits: counters published (main), read-name total published (side)
   // growable finalize scratch
@@ -440,6 +441,31 @@ struct SideStream {
     b->cur = b->stream; b->cur_slot = 0;
   }
 };
+// The grouped kernel of the refine / call stage beside the wave-per-item kernel of the same stage (the table kernel in front of the
+// stage has split the items between them): for the lifetime of this object launches go to the fourth stream - idle from the start
+// of a pass until d3_taskoff -, which starts behind what the main stream holds at this point.  join_classes: the main stream waits for
+// it.  Only the handles whose passes are eager by the library's rule do this (graph_mode 0: batches above the launch-bound size, or
+// SNF_GRAPH=0).  A handle that replays its passes from a graph keeps one stream here, in the capture and in its few eager passes (the
+// first two, the sampled ones) alike: a launch-bound batch has nothing to overlap, and the two event edges per stage cost it more than
+// that - chr20 alone 0.35 against 0.27 ms per step when its eager passes forked too.
+static bool classes_beside(const snf_batch_impl* b) { return !b->capturing && b->graph_mode == 0; }
+struct ClassFork {
+  snf_batch_impl* b; bool on;
+  ClassFork(snf_batch_impl* b_) : b(b_), on(classes_beside(b_)) {
+    if (!on) return;
+    SNF_HIP(hipEventRecord(b->ev_cls_fork, b->stream));
+    SNF_HIP(hipStreamWaitEvent(b->stream4, b->ev_cls_fork, 0));
+    b->cur = b->stream4;
+  }
+  ~ClassFork() {
+    if (!on) return;
+    (void)hipEventRecord(b->ev_cls_join, b->stream4);
+    b->cur = b->stream;
+  }
+};
+void join_classes(snf_batch_impl* b) {
+  if (classes_beside(b)) SNF_HIP(hipStreamWaitEvent(b->stream, b->ev_cls_join, 0));
+}
 void join_side(snf_batch_impl* b) {  // main stream waits for everything enqueued on the side stream so far
   SNF_HIP(hipStreamWaitEvent(b->stream, b->ev_join, 0));
 }
@@ -1019,6 +1045,8 @@ void do_upload(snf_batch_impl* b) {
   v.big_cap = (int64_t)(N1 / 64 + 2); v.big_cnt = dalloc<uint32_t>(b, 3 * 64 * 16); v.big_list = dalloc<int32_t>(b, (size_t)(3 * 64 * v.big_cap));
   v.big_wave = v.wave_path;
   { const int hn = b->k.heavy_n; v.heavy_n = hn > 8 && hn < 64 ? hn : 0; }      // (0 / out of range: one class, as before)
+  v.d1_push = v.wave_path && b->k.d1_groups ? 1 : 0;                             // (c4_emit / d1b_emit build the lists of the wave-per-item kernels)
+  v.d2_push = v.wave_path && b->k.d2_groups ? (b->k.d2_mid ? 2 : 1) : 0;
   { const int eb = b->k.e1_batch; v.e1_batch = (eb == 2 || eb == 4 || eb == 8 || eb == 16 || eb == 32) ? eb : 64; }
   v.stage_cap = b->k.big_stage ? 1 : 0;
   v.cdesc = dalloc<ConsDesc>(b, N1); v.crl_off = dalloc<int64_t>(b, N1); v.crl_len = dalloc<int32_t>(b, N1); v.aln_kept_w = dalloc<uint8_t>(b, N1);
@@ -1306,6 +1334,7 @@ void enqueue_pass_init(snf_batch_impl* b) {
     if (TS_SLOTS * v.super_stride > n0) n0 = TS_SLOTS * v.super_stride;
     if ((int64_t)(sizeof(Counts) / 8) > n0) n0 = (int64_t)(sizeof(Counts) / 8);
     if (3 * 64 * 16 > n0) n0 = 3 * 64 * 16;
+    if (v.tile_stride > n0) n0 = v.tile_stride;
     FUSED(z0_init, n0);
   } else {
     dzero(b, v.cnt, sizeof(Counts));
@@ -1466,9 +1495,11 @@ void run_call_candidates(snf_batch_impl* b) {
     }
     if (b->k.readprep == 3) fork_mark(b);   // mode 3: the read preparation may only start once stages A-C are through
     if (v.wave_path && b->k.d1_groups) {
-      // merge_inner / resplit by cluster size (snf_wave_refine_g.h): eight clusters of <= 8 leads per wave, then d1w_refine - a wave
-      // per cluster - for what that kernel handed on
-      { Scope _s(b, "d1g_refine8", N * 36 / 3);
+      // merge_inner / resplit by cluster size (snf_wave_refine_g.h): eight clusters of <= 8 leads per wave, and d1w_refine - a wave
+      // per cluster - for the others, which c4_emit has listed.  The two share no cluster and no output entry: in an eager pass the
+      // grouped kernel goes beside the other one (ClassFork), in a captured pass they stay in line
+      { ClassFork _f(b);
+        Scope _s(b, "d1g_refine8", N * 36 / 3);
         hipLaunchKernelGGL(d1g_refine<8>, dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
         SNF_HIP(hipGetLastError()); }
       { Scope _s(b, "d1w_refine", N * 36 - N * 36 / 3);
@@ -1476,6 +1507,7 @@ void run_call_candidates(snf_batch_impl* b) {
         hipLaunchKernelGGL(d1w_refine, dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
         v.d1_from_list = 0;
         SNF_HIP(hipGetLastError()); }
+      join_classes(b);      // (x_big<0> and the rc table need both)
     } else if (v.wave_path) {
       Scope _s(b, "d1w_refine", N * 36);
       hipLaunchKernelGGL(d1w_refine, dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
@@ -1493,20 +1525,20 @@ void run_call_candidates(snf_batch_impl* b) {
   if (b->k.readprep == 1 || b->k.readprep == 3) enqueue_read_prep(b);  // while the long refine kernel keeps the main stream busy
   if (N > 0) {
     if (b->fused && v.chain_on) CHAIN(d1bc_rctable, N);
-    else if (b->fused) {
-      FUSED(d1a_count, N);
-      FUSED(d1bk_rctable, N);
-    } else {
+    else if (b->fused) FUSED(d1bk_rctable, N);      // (the tile sums of rcflag: published by rc_emit)
+    else {
       prim_exscan<uint32_t>(b, v.rcflag, v.rcscan, N + 1, "scan_refined");
       LAUNCH_Q(d1b_rctable, v, N, N * 4);
     }
     if (v.wave_path && b->k.d2_groups) {
-      // call_from by cluster size (snf_wave_call_g.h): eight clusters of <= 8 leads per wave, then two of <= 32 from the list
-      // the first kernel left, then d2w_call - a wave per cluster - for what the second handed on
+      // call_from by cluster size (snf_wave_call_g.h): eight clusters of <= 8 leads per wave; d2w_call - a wave per cluster - for the
+      // others, from the list d1b_emit built (with the mid class: two of <= 32 per wave from list 0, d2w_call from list 1).  As in the
+      // refine stage the grouped kernel of an eager pass runs beside the others
       const bool ph = b->cfg.phase != 0;
       // (32 B per signature for the call stage, split by the share of the leads each kernel sees on a 30x genome - a third of
       //  them sit in refined clusters of at most eight leads)
-      { Scope _s(b, "d2g_call8", N * 32 / 3);
+      { ClassFork _f(b);
+        Scope _s(b, "d2g_call8", N * 32 / 3);
         if (ph) hipLaunchKernelGGL((d2g_call<8, 4, true>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         else hipLaunchKernelGGL((d2g_call<8, 4, false>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         SNF_HIP(hipGetLastError()); }
@@ -1520,6 +1552,7 @@ void run_call_candidates(snf_batch_impl* b) {
         hipLaunchKernelGGL(b->k_d2w, dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         v.d2_from_list = 0;
         SNF_HIP(hipGetLastError()); }
+      join_classes(b);      // (x_big<1> and the compaction need both)
     } else if (v.wave_path) {
       Scope _s(b, "d2w_call", N * 32);
       hipLaunchKernelGGL(b->k_d2w, dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
@@ -1533,10 +1566,8 @@ void run_call_candidates(snf_batch_impl* b) {
       SNF_HIP(hipGetLastError());
     }
     if (b->fused && v.chain_on) CHAIN(d3cc_compact, N);
-    else if (b->fused) {
-      FUSED(d3a_count, N);
-      FUSED(d3ck_compact, N);
-    } else {
+    else if (b->fused) FUSED(d3ck_compact, N);      // (the tile sums of cdflag: published where a candidate is written)
+    else {
       prim_exscan<uint32_t>(b, v.cdflag, v.cdscan, N + 1, "scan_calls");
       LAUNCH_Q(d3_compact, v, N, 0);
     }
@@ -2672,6 +2703,8 @@ int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out) {
     SNF_HIP(hipEventCreateWithFlags(&b->ev_join4, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_e3, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_fork3, hipEventDisableTiming));
+    SNF_HIP(hipEventCreateWithFlags(&b->ev_cls_fork, hipEventDisableTiming));
+    SNF_HIP(hipEventCreateWithFlags(&b->ev_cls_join, hipEventDisableTiming));
     SNF_HIP(hipEventCreate(&b->ev_base));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_counts, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_rn, hipEventDisableTiming));
@@ -2759,6 +2792,8 @@ void snf_batch_destroy(snf_batch_t* bb) {
   if (b->stream3) (void)hipStreamSynchronize(b->stream3);
   if (b->stream4) (void)hipStreamSynchronize(b->stream4);
   if (b->ev_fork3) (void)hipEventDestroy(b->ev_fork3);
+  if (b->ev_cls_fork) (void)hipEventDestroy(b->ev_cls_fork);
+  if (b->ev_cls_join) (void)hipEventDestroy(b->ev_cls_join);
   if (b->ev_e3) (void)hipEventDestroy(b->ev_e3);
   if (b->ev_base) (void)hipEventDestroy(b->ev_base);
   if (b->ev_counts) (void)hipEventDestroy(b->ev_counts);

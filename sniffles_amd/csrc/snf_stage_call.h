@@ -56,11 +56,43 @@ struct LessFaPosbinIdx {
   }
 };
 
-SNF_HD void rc_emit(const View& v, int32_t pos, int32_t n, int32_t c, bool keeplong) {
+// Whoever sets a flag of a "flags -> scan -> emit" chain (snf_fused.h) counts it into the flag's 256-element tile right away: the
+// emit kernel of the chain then finds the tile sums in place, and no launch has to read the whole flag array back only to count it
+// (slots TS_REFINED / TS_CALLS; z0_init zeroes their rows at the start of the pass).  A flag is set at most once per pass.
+SNF_HD void flag_publish(const View& v, int slot, int64_t i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (v.wave_uniform && (threadIdx.x & 63) != 0) return;      // (x_big: the 64 lanes run one serial body, the flag is one flag)
+#endif
+  atomic_add_u64(&v.tile_sums[(int64_t)slot * v.tile_stride + (i >> 8)], 1ull);
+}
+// wave form - every lane of the wave calls it, `set` says whether the lane has set flag i: the lanes whose flags share a tile share
+// one atomic (a wave's flags lie next to each other: one or two rounds)
+SNF_D void flag_publish_wave(const View& v, int slot, bool set, int64_t i) {
+  const int lane = (int)(threadIdx.x & 63), tile = (int)(i >> 8);
+  unsigned long long todo = __ballot(set);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const int t = __builtin_amdgcn_readlane(tile, leader);
+    const unsigned long long same = __ballot(set && tile == t);
+    if (lane == leader) atomicAdd(&v.tile_sums[(int64_t)slot * v.tile_stride + t], (unsigned long long)__builtin_popcountll(same));
+    todo &= ~same;
+  }
+}
+
+SNF_HD void rc_store(const View& v, int32_t pos, int32_t n, int32_t c, bool keeplong) {
   v.rcflag[pos] = 1;
   v.rc_n_s[pos] = n;
   v.rc_cl_s[pos] = c;
   v.rc_keeplong_s[pos] = keeplong ? 1 : 0;
+}
+SNF_HD void rc_emit(const View& v, int32_t pos, int32_t n, int32_t c, bool keeplong) {
+  rc_store(v, pos, n, c, keeplong);
+  flag_publish(v, TS_REFINED, pos);
+}
+// every lane of the wave calls it; the lanes with `emit` each start a refined cluster
+SNF_D void rc_emit_wave(const View& v, bool emit, int32_t pos, int32_t n, int32_t c, bool keeplong) {
+  if (emit) rc_store(v, pos, n, c, keeplong);
+  flag_publish_wave(v, TS_REFINED, emit, pos);
 }
 
 // room for a fused sequence behind the input sequences; in a wave that runs the body uniformly one lane reserves for all
@@ -259,11 +291,23 @@ SNF_HD void d1b_rctable_body(int64_t pos, const View& v) {
   d1b_emit(pos, v);
 }
 SNF_HD void d1b_emit(int64_t pos, const View& v) {
+  int32_t hand_r = 0, hand_n = 0;
   if (pos < v.cnt->NF && v.rcflag[pos]) {
     uint32_t r = v.rcscan[pos];
-    v.rc_lo[r] = (int32_t)pos; v.rc_n[r] = v.rc_n_s[pos]; v.rc_cluster[r] = v.rc_cl_s[pos];
+    const int32_t n = v.rc_n_s[pos];
+    v.rc_lo[r] = (int32_t)pos; v.rc_n[r] = n; v.rc_cluster[r] = v.rc_cl_s[pos];
     v.rc_keeplong[r] = v.rc_keeplong_s[pos];
+    if (n > 8) { hand_r = (int32_t)r; hand_n = n; }
   }
+#if defined(__HIP_DEVICE_COMPILE__)
+  // refined clusters that do not fit a group of d2g_call<8>: list 0 for d2w_call; with the mid class on (View::d2_push == 2) list 0
+  // holds those of at most 32 leads for d2g_call<32>, list 1 the others for d2w_call
+  if (v.d2_push) {
+    const bool second = v.d2_push == 2 && hand_n > 32;
+    d2list_push(v, 0, hand_n > 0 && !second, hand_r, hand_n, pos);
+    if (v.d2_push == 2) d2list_push(v, 1, second, hand_r, hand_n, pos);
+  }
+#endif
 }
 
 // ------------------------------------------------------------------------------------------ D2
@@ -449,6 +493,7 @@ SNF_HD void d2_call_body(int64_t r, const View& v) {
 #undef SNF_UNI_SUM
   v.candx[r] = x;
   v.cdflag[r] = 1;
+  flag_publish(v, TS_CALLS, r);
 }
 
 // D3a: compaction (cdscan = exclusive scan of cdflag) -> calls in candidate order

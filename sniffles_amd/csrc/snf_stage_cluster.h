@@ -470,6 +470,44 @@ SNF_HD void c3_serial_body(int64_t g, const View& v) {
   atomic_add_u64((unsigned long long*)&v.cnt->n_dirty_groups, 1ull);
 }
 
+// ------------------------------------------------------------------------------------------ striped hand-over lists (View::d2_list)
+// The stages behind a table kernel run as two kernels by item size - the grouped kernel walks the table and takes the items of at
+// most 8 leads, the wave-per-item kernel takes the others from a list (consumer side: d2list_prefix / d2list_at, snf_wave_call.h).
+// The size is known when the table entry is written, so the table kernel builds the list (c4_emit: list 2, merged clusters for
+// d1w_refine; d1b_emit: lists 0 / 1, refined clusters for d2g_call<32> / d2w_call) and the two kernels of a stage need not wait for each
+// other.  Producer side - every lane of the wave that runs the emit body calls it, the lanes with `hand` append `item`; one atomic
+// per wave and stripe.  `nleads`: the item's size, `pos`: the position of its first lead (L / F index space).
+// The kernel that walks the list starts its workgroups in index order and takes a few items each: a cluster of 60 leads costs several
+// times what one of 10 does, and when such items sit anywhere in the list the kernel ends with a handful of waves working through
+// them (d1w_refine: 4096 waves in flight for 40 us, fewer than 30 for the following 45 us).  Items above View::heavy_n go to stripes
+// 0..15 - the front of the consumer's index space -, the others to stripes 16..63.
+// The stripe is the 256-position tile of `pos` (in d1b_emit: the producer's workgroup; in c4_emit, whose index space is the seeds,
+// the tile of the cluster's first lead) modulo the S = 64, 16 or 48 stripes of the class.  Consecutive tiles go to different stripes,
+// so a stripe takes the items that start in at most NS / (256 S) + 1 tiles; a listed item has at least 9 leads and occupies as many
+// positions of its own, so at most 29 start in one tile.  That is fewer than NS / (8 S) + 29 entries, with S >= 16 below
+// d2cap = N / 64 + 64: a stripe cannot overflow from these producers (the check stays - it is what keeps the store in bounds).
+SNF_D void d2list_push(const View& v, int k, bool hand, int32_t item, int nleads, int64_t pos) {
+  const int lane = (int)(threadIdx.x & 63);
+  const unsigned tile = (unsigned)(pos >> 8);
+  const int stripe = v.heavy_n <= 0 ? (int)(tile & 63u) : nleads > v.heavy_n ? (int)(tile & 15u) : 16 + (int)(tile % 48u);
+  unsigned long long todo = __ballot(hand);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const int st = __builtin_amdgcn_readlane(stripe, leader);
+    const bool mine = hand && stripe == st;
+    const unsigned long long hm = __ballot(mine);
+    uint32_t at = 0;
+    if (lane == leader) at = atomicAdd(&v.d2cnt[(k * 64 + st) * 16], (uint32_t)__builtin_popcountll(hm));
+    at = (uint32_t)__builtin_amdgcn_readlane((int)at, leader);
+    if (mine) {
+      const int64_t slot = (int64_t)at + __builtin_popcountll(hm & ((1ull << lane) - 1ull));
+      if (slot < v.d2cap) v.d2_list[k][(int64_t)st * v.d2cap + slot] = item;
+      else atomicOr(&v.cnt->overflow, 2);
+    }
+    todo &= ~hm;
+  }
+}
+
 // C4: merged cluster table (clscan = exclusive scan of clflag)
 SNF_HD void c4_emit(int64_t s, const View& v);
 SNF_HD void c4_clusters_body(int64_t s, const View& v) {
@@ -477,6 +515,7 @@ SNF_HD void c4_clusters_body(int64_t s, const View& v) {
   c4_emit(s, v);
 }
 SNF_HD void c4_emit(int64_t s, const View& v) {
+  int32_t hand_c = 0, hand_n = 0, hand_lo = 0;
   if (s < v.cnt->n_seeds && v.clflag[s]) {
     const uint32_t c = v.clscan[s];
     v.cl_head[c] = (int32_t)s;
@@ -484,7 +523,11 @@ SNF_HD void c4_emit(int64_t s, const View& v) {
     hd.h = (int32_t)s; hd.lo = v.seed_lo[s]; hd.n = v.seed_hi[v.c_last[s]] - hd.lo; hd.grp = v.seed_grp[s]; hd.repeat = v.c_repeat[s];
     hd._pad[0] = hd._pad[1] = hd._pad[2] = 0;
     v.chdr[c] = hd;
+    if (hd.n > 8) { hand_c = (int32_t)c; hand_n = hd.n; hand_lo = hd.lo; }
   }
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (v.d1_push) d2list_push(v, 2, hand_n > 0, hand_c, hand_n, hand_lo);      // clusters that do not fit a group of d1g_refine<8>: d1w_refine
+#endif
 }
 
 }  // namespace snf

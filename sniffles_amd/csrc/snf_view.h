@@ -285,11 +285,13 @@ struct View {
 #ifdef SNF_WG_TRACE
   unsigned long long* wgtrace;   // measurement build only (-DSNF_WG_TRACE): per consensus call {start, duration | shape} in 100 MHz ticks
 #endif
-  // refined clusters handed on by the grouped call kernels (snf_wave_call_g.h): list 0 more than 8 leads (d2g_call<8> -> <32>),
-  // list 1 more than 32 (-> d2w_call).  64 stripes per list (stripe = workgroup & 63) with a counter each, d2cnt[(list * 64 +
-  // stripe) * 16]: ten thousand returning atomics on ONE counter took 0.1 ms by themselves.  Stripe s owns d2_list[k][s * d2cap ...)
-  // list 2: merged clusters of more than 8 leads, handed by d1g_refine<8> to d1w_refine (snf_wave_refine_g.h)
+  // items the grouped kernels leave to the next size class, listed by the table kernel in front of the stage (d2list_push,
+  // snf_stage_cluster.h).  Refined clusters (d1b_emit): list 0 more than 8 leads (-> d2w_call; with the mid class 9..32 -> d2g_call<32>),
+  // list 1 more than 32 (mid class only, -> d2w_call).  64 stripes per list with a counter each, d2cnt[(list * 64 + stripe) * 16]: ten
+  // thousand returning atomics on ONE counter took 0.1 ms by themselves.  Stripe s owns d2_list[k][s * d2cap ...)
+  // list 2: merged clusters of more than 8 leads (c4_emit -> d1w_refine)
   int32_t* d2_list[3]; uint32_t* d2cnt; int64_t d2cap;
+  int32_t d1_push, d2_push;  // the table kernels build list 2 (grouped refine on) / lists 0, 1 (grouped call on: 1, with the mid class: 2)
   int32_t d2_from_list, d1_from_list;   // != 0: this launch of d2w_call takes its refined clusters from d2_list[d2_from_list - 1] / d1w_refine its clusters from list 2
   int32_t* cls_list[8];      // cons ids per work list (see Counts::n_cls; 6 unused), appended with wave-aggregated atomics
   // clusters / refined clusters / calls with more than 64 leads, collected by the wave kernels (kind 0 d1w_refine, 1 d2w_call,

@@ -131,29 +131,7 @@ SNF_D int32_t d2list_at(const View& v, int k, int64_t i, const int32_t* pre) {
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (pre[mid] <= (int32_t)i) lo = mid; else hi = mid - 1; }
   return v.d2_list[k][(int64_t)lo * v.d2cap + (i - pre[lo])];
 }
-// producer side: the lanes with `hand` append their cluster to list k, one atomic per wave on the workgroup's stripe.
-// `nleads`: the item's size.  The kernel that walks the list starts its workgroups in index order and takes a few items each: a
-// cluster of 60 leads costs several times what one of 10 does, and when such items sit anywhere in the list the kernel ends with a
-// handful of waves working through them (d1w_refine: 4096 waves in flight for 40 us, fewer than 30 for the following 45 us).  Items
-// above View::heavy_n go to stripes 0..15 - the front of the consumer's index space -, the others to stripes 16..63.
-SNF_D void d2list_push(const View& v, int k, bool hand, int32_t r, int lane, int nleads = 0) {
-  const bool split = v.heavy_n > 0;
-  for (int cls = 0; cls < 2; cls++) {
-    const bool mine = hand && (!split ? cls == 0 : (nleads > v.heavy_n) == (cls == 0));
-    const unsigned long long hm = __ballot(mine);
-    if (!hm) continue;
-    const int stripe = !split ? (int)(blockIdx.x & 63) : cls == 0 ? (int)(blockIdx.x & 15) : 16 + (int)(blockIdx.x % 48u);
-    const int leader = __builtin_ctzll(hm);
-    uint32_t at = 0;
-    if (lane == leader) at = atomicAdd(&v.d2cnt[(k * 64 + stripe) * 16], (uint32_t)__builtin_popcountll(hm));
-    at = (uint32_t)__builtin_amdgcn_readlane((int)at, leader);
-    if (mine) {
-      const int64_t slot = (int64_t)at + __builtin_popcountll(hm & ((1ull << lane) - 1ull));
-      if (slot < v.d2cap) v.d2_list[k][(int64_t)stripe * v.d2cap + slot] = r;
-      else atomicOr(&v.cnt->overflow, 2);      // (a stripe holds a 64th of all LEADS + 64 entries; the items of either class are at least 9 times fewer)
-    }
-  }
-}
+// (producer side: d2list_push, snf_stage_cluster.h - the table kernels in front of each stage build the lists)
 
 // ------------------------------------------------------------------------------------------ lead aggregates of a call
 // len(set(strands)), leads close to a read edge (postprocessing.py:574-577), the HP / PS majorities of phase_sv over distinct
@@ -225,7 +203,7 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t
   __shared__ RankLds rl;
   const int lane = threadIdx.x;
   const snf_config_t& cfg = v.cfg;
-  // the refined clusters of this launch: all of them, or (View::d2_from_list) the ones the grouped kernels handed on
+  // the refined clusters of this launch: all of them, or (View::d2_from_list) the ones d1b_emit listed for this kernel
   // (more than 32 leads, snf_wave_call_g.h)
   __shared__ int32_t d2pre[65];
   const bool from_list = v.d2_from_list != 0;      // 1 + the list's number
@@ -419,6 +397,7 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2w_call(const View v, int64_t
     if (lane == 0) {
       v.candx[r] = x;
       v.cdflag[r] = 1;
+      flag_publish(v, TS_CALLS, r);
     }
     __syncthreads();
   }

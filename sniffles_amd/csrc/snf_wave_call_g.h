@@ -5,9 +5,10 @@
 // 15-30): 7 of 64 lanes worked on average, and the per-cluster chain of dependent loads was paid 94 000 times per pass.
 // Here a wave is cut into 64 / G groups of G lanes (G = 8, then 32) and every group takes a cluster of at most G leads: the
 // same arithmetic, every wave-wide primitive of d2w_call replaced by its group-wide form (ballots sliced per group, shuffles
-// inside the group, LDS scratch indexed from the group's base lane).  A cluster that does not fit a group is handed on:
-// d2g_call<8> -> list 0 -> d2g_call<32> -> list 1 -> d2w_call -> (more than 64 leads) x_big<1>.  Results are indexed by the
-// refined cluster's id, so the order in which the kernels get to a cluster does not matter.
+// inside the group, LDS scratch indexed from the group's base lane).  A cluster that does not fit a group is skipped: the table
+// kernel in front of the stage (d1b_emit) has put it on the list of the kernel that takes it - list 0 for d2w_call, or (SNF_D2_MID)
+// list 0 for d2g_call<32> and list 1 for d2w_call; more than 64 leads: d2w_call -> x_big<1>.  Results are indexed by the refined
+// cluster's id and the kernels share no item, so they run beside each other and the order in which a cluster is reached does not matter.
 //
 // Control flow is wave-uniform throughout: a group whose cluster is screened out, or that has no cluster, keeps executing with
 // its predicate off (the collectives of the other groups need every lane).
@@ -200,7 +201,7 @@ SNF_D void group_lead_agg(const snf_config_t& cfg, CallLds& lds, int gl, int gba
   }
 }
 
-// LIST: the items are the entries of hand-over list 0 (clusters d2g_call<8> handed on); otherwise every refined cluster
+// LIST: the items are the entries of hand-over list 0 (the refined clusters of 9..32 leads); otherwise every refined cluster
 template <int G, int MINW, bool PHASE>
 __global__ void __launch_bounds__(SNF_WAVE, MINW) d2g_call(const View v, int64_t n_unused) {
   IT_SCOPE(6)
@@ -235,9 +236,7 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2g_call(const View v, int64_t
     bool valid = cur.valid;
     const int32_t r = cur.r;
     int32_t flo = cur.flo, n = cur.n, c = cur.c, h = cur.h;
-    // clusters that do not fit a group go to the next kernel's list
-    d2list_push(v, LIST ? 1 : 0, valid && n > G && gl == 0, r, lane, n);
-    if (valid && n > G) valid = false;
+    if (valid && n > G) valid = false;      // clusters that do not fit a group: on the next kernel's list (d1b_emit)
     if (!valid) n = 0;
     int nmax = n;
 #pragma unroll
@@ -435,6 +434,7 @@ __global__ void __launch_bounds__(SNF_WAVE, MINW) d2g_call(const View v, int64_t
       v.candx[r] = x;
       v.cdflag[r] = 1;
     }
+    flag_publish_wave(v, TS_CALLS, alive && gl == 0, r);
     __syncthreads();
   }
 }

@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(SNF_WAVE) d1w_refine(const View v, int64_t n_u
   __shared__ WaveLds lds;
   const int lane = threadIdx.x;
   const snf_config_t& cfg = v.cfg;
-  // the clusters of this launch: all of them, or (View::d1_from_list) those d1g_refine<8> handed on through list 2
+  // the clusters of this launch: all of them, or (View::d1_from_list) those c4_emit put on list 2 (more than 8 leads)
   __shared__ int32_t d1pre[65];
   const bool from_list = v.d1_from_list != 0;
   const int64_t n_clusters = from_list ? d1list_prefix(v, lane, d1pre) : v.cnt->n_clusters;
@@ -317,10 +317,10 @@ __global__ void __launch_bounds__(SNF_WAVE) d1w_refine(const View v, int64_t n_u
       const bool brk = fact && (lane == 0 || p_fa != s_fa || (s_pb - p_pb > thr));
       const unsigned long long bmask = __ballot(brk);
       if (fact) v.FI[lo + lane] = lo + s_j;
-      if (brk) {
+      {
         unsigned long long above = (lane < 63) ? (bmask >> (lane + 1)) : 0ull;
         const int end = above ? lane + 1 + __builtin_ctzll(above) : m;  // exclusive: position of the next chain start
-        rc_emit(v, lo + lane, end - lane, (int32_t)c, false);
+        rc_emit_wave(v, brk, lo + lane, end - lane, (int32_t)c, false);
       }
       continue;
     }
@@ -390,7 +390,7 @@ __global__ void __launch_bounds__(SNF_WAVE) d1w_refine(const View v, int64_t n_u
       }
       const int32_t my_out = __shfl(SEGOUT, sidx < 0 ? 0 : sidx, SNF_WAVE), my_st = __shfl(ST, sidx < 0 ? 0 : sidx, SNF_WAVE);
       if (fact) v.FI[lo + my_out + (lane - my_st)] = lo + s_k;
-      if (lane < cntc) rc_emit(v, lo + RCS, RCL, (int32_t)c, true);
+      rc_emit_wave(v, lane < cntc, lo + RCS, RCL, (int32_t)c, true);
       __syncthreads();
     }
   }

@@ -5,8 +5,9 @@
 // on average - one lane in eight had a lead.  Here a wave is cut into 64 / G groups of G = 8 lanes and every group takes a cluster of
 // at most G leads, with the arithmetic of d1w_refine and every wave-wide primitive in its group-wide form (the pattern of
 // d2g_call<8>, snf_wave_call_g.h): ballots sliced per group, shuffles inside the group, the sequential bin-merge state machine of
-// resplit stepped in lock-step by all groups that still have work.  Clusters with more leads go to hand-over list 2, which
-// d1w_refine walks next (it passes those beyond 64 leads on to x_big<0>).  Both kernels write the same F / FI / refined-cluster tables.
+// resplit stepped in lock-step by all groups that still have work.  Clusters with more leads are skipped: they are on hand-over list 2
+// (c4_emit), which d1w_refine walks beside this kernel (it passes those beyond 64 leads on to x_big<0>).  Both kernels write the same
+// F / FI / refined-cluster tables, each the entries of its own clusters.
 //
 // Control flow is wave-uniform throughout: a group that is done, or has no cluster, keeps executing with its predicate off.
 #pragma once
@@ -53,9 +54,7 @@ __global__ void __launch_bounds__(SNF_WAVE) d1g_refine(const View v, int64_t n_u
     hd_nxt = header(base + 2 * stride);
     const int64_t c = base + gi;
     bool valid = c < n_clusters && hd.n > 0;
-    // clusters that do not fit a group: d1w_refine, from list 2
-    d2list_push(v, 2, valid && hd.n > G && gl == 0, (int32_t)c, lane, hd.n);
-    if (hd.n > G) valid = false;
+    if (hd.n > G) valid = false;      // clusters that do not fit a group: d1w_refine, from list 2 (c4_emit put them there)
     const int32_t lo = hd.lo, n = valid ? hd.n : 0;
     const int nmax = __builtin_amdgcn_readfirstlane(wave_max32(n));
     if (nmax == 0) continue;
@@ -179,11 +178,12 @@ __global__ void __launch_bounds__(SNF_WAVE) d1g_refine(const View v, int64_t n_u
 
     // ---- resplit_bnd: group by (mate_contig, is_first) in first-appearance order, chain 1-kb bins
     const bool bnd = valid && svtype == SNF_BND;
-    if (bnd && (m <= 1 || cfg.dev_no_resplit)) {
+    const bool whole_bnd = bnd && (m <= 1 || cfg.dev_no_resplit);
+    if (whole_bnd) {
       if (fact) v.FI[lo + gl] = lo + gl;
-      if (gl == 0) rc_emit(v, lo, m, (int32_t)c, true);
       done = true;
     }
+    rc_emit_wave(v, whole_bnd && gl == 0, lo, m, (int32_t)c, true);
     const bool bnd2 = bnd && !done;
     if (__ballot(bnd2)) {
       const int thr = cfg.cluster_merge_bnd;
@@ -205,19 +205,19 @@ __global__ void __launch_bounds__(SNF_WAVE) d1g_refine(const View v, int64_t n_u
       const bool brk = ab && (gl == 0 || p_fb != s_fb || (s_pb - p_pb > thr));
       const unsigned long long bmask = gballot<G>(brk, gbase);
       if (ab) v.FI[lo + gl] = lo + s_j;
-      if (brk) {
+      {
         const unsigned long long above = (gl < G - 1) ? (bmask >> (gl + 1)) : 0ull;
         const int end = above ? gl + 1 + __builtin_ctzll(above) : m;  // exclusive: position of the next chain start
-        rc_emit(v, lo + gl, end - gl, (int32_t)c, false);
+        rc_emit_wave(v, brk, lo + gl, end - gl, (int32_t)c, false);
       }
       if (bnd2) done = true;
       __syncthreads();
     }
 
     // ---- resplit on |svlen| bins of 20 (cluster.py:125-161)
-    if (!done && (cfg.dev_no_resplit_repeat || cfg.dev_no_resplit)) {
+    const bool whole_cfg = !done && (cfg.dev_no_resplit_repeat || cfg.dev_no_resplit);
+    if (whole_cfg) {
       if (fact) v.FI[lo + gl] = lo + gl;
-      if (gl == 0) rc_emit(v, lo, m, (int32_t)c, true);
       done = true;
     }
     const int rb = cfg.cluster_resplit_binsize;
@@ -225,11 +225,12 @@ __global__ void __launch_bounds__(SNF_WAVE) d1g_refine(const View v, int64_t n_u
     const int32_t bin = (int32_t)((av / (uint32_t)rb) * (uint32_t)rb);
     // one bin: the cluster stays whole, in its order
     const int32_t bin0 = gshfl_i32<G>(bin, 0, gbase);
-    if (!done && gballot<G>(fact && bin != bin0, gbase) == 0ull) {
+    const bool whole_bin = !done && gballot<G>(fact && bin != bin0, gbase) == 0ull;
+    if (whole_bin) {
       if (fact) v.FI[lo + gl] = lo + gl;
-      if (gl == 0) rc_emit(v, lo, m, (int32_t)c, true);
       done = true;
     }
+    rc_emit_wave(v, (whole_cfg || whole_bin) && gl == 0, lo, m, (int32_t)c, true);   // (the usual case: one atomic per wave and tile)
     if (__ballot(!done) == 0ull) continue;
     {
       const bool rs = !done;                    // (group-uniform) this group's cluster is split by |svlen| bins
@@ -294,7 +295,7 @@ __global__ void __launch_bounds__(SNF_WAVE) d1g_refine(const View v, int64_t n_u
       const int sx = sidx < 0 ? 0 : sidx;
       const int32_t my_out = gshfl_i32<G>(SEGOUT, sx, gbase), my_st = gshfl_i32<G>(ST, sx, gbase);
       if (ar) v.FI[lo + my_out + (gl - my_st)] = lo + s_k;
-      if (rs && gl < cntc) rc_emit(v, lo + RCS, RCL, (int32_t)c, true);
+      rc_emit_wave(v, rs && gl < cntc, lo + RCS, RCL, (int32_t)c, true);
       __syncthreads();
     }
   }
