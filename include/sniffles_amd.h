@@ -824,6 +824,31 @@ typedef struct snf_bai_run_result {
 int snf_bai_run(snf_bgzf_t* z, const int64_t* member_file_off, const snf_bai_carry_t* in, snf_bai_run_result_t* out);
 const char* snf_bai_last_error(void);
 
+/* -----------------------------------------------------------------------------------------------------------------
+ * BGZF deflate on the device (csrc/snf_deflate.h): bytes + the caller's member cuts -> a run of complete BGZF members
+ * (18-byte header with BSIZE, raw deflate with dynamic Huffman codes or one stored block, CRC-32, ISIZE) as one
+ * contiguous file image.  The reference's counterpart is pysam.tabix_index / bgzip behind `--vcf out.vcf.gz` and
+ * gzip.compress in the SNF writer.  No EOF marker is appended (a member of 0 bytes is one).
+ * SNF_DEFLATE_GRID is read at every snf_deflate_run.
+ * ----------------------------------------------------------------------------------------------------------------- */
+typedef struct snf_deflate_result {
+  const uint8_t* image;        /* host, image_len bytes: the members one behind the other */
+  int64_t image_len;
+  const int64_t* member_off;   /* host, n_members + 1: offset of every member in the image, and image_len */
+  int64_t n_members;
+  float ms_kernel;             /* HIP events around deflate_member, the scan and deflate_pack */
+  float _pad;
+} snf_deflate_result_t;
+
+typedef struct snf_deflate snf_deflate_t;
+int snf_deflate_create(int device, snf_deflate_t** out);
+/* `member_len[n_members]`: input bytes of every member, each at most 65280 (0xff00), together `len`; anything else fails the
+ * call with a message.  The result is library-owned until the next snf_deflate_run / destroy on the handle. */
+int snf_deflate_run(snf_deflate_t* z, const uint8_t* data, int64_t len, const uint32_t* member_len, int64_t n_members,
+                    snf_deflate_result_t* out);
+void snf_deflate_destroy(snf_deflate_t* z);
+const char* snf_deflate_last_error(void);
+
 /* snf_extract_upload for a blob and a record table that are in HBM already (an snf_bgzf_t's, which must outlive the use):
  * in->records and in->rec_off are DEVICE pointers on `device` - rec_off may point into the middle of the file's table, its
  * offsets are relative to in->records; in->qname_rank and the contig tables are host pointers.  `heads`: host, n_records x 6 as

@@ -464,6 +464,12 @@ class snf_bai_run_result_t(C.Structure):
                 ("ms_runs", C.c_float), ("_pad2", C.c_float)]
 
 
+# ---- BGZF deflate on the device (snf_deflate_*, csrc/snf_deflate.h)
+class snf_deflate_result_t(C.Structure):
+    _fields_ = [("image", u8p), ("image_len", i64), ("member_off", C.POINTER(C.c_int64)), ("n_members", i64),
+                ("ms_kernel", C.c_float), ("_pad", C.c_float)]
+
+
 def extract_config_struct(cfg) -> snf_extract_config_t:
     """`cfg`: anything with the SnifflesConfig attribute names extraction reads (config.py:190-215, 507-617)."""
     g = lambda name, default: getattr(cfg, name, default)

@@ -1020,6 +1020,7 @@ SNF_HD void x_totals_body(int64_t i, const ExView& v) {
 }  // namespace snf
 #include "snf_bgzf.h"
 #include "snf_bamindex.h"
+#include "snf_deflate.h"
 using namespace snf;
 SNF_KERNEL(x_count, ExView)
 SNF_KERNEL(x_emit, ExView)
@@ -1785,6 +1786,117 @@ void snf_bgzf_destroy(snf_bgzf_t* z) {
   x_release(z->dev); x_release(z->bai_dev);
   for (hipEvent_t e : z->ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : z->bev) if (e) (void)hipEventDestroy(e);
+  delete z;
+}
+}
+
+// ================================================================================= BGZF deflate: host side ====
+struct snf_deflate {
+  int device = 0;
+  XSlab slab;                    // one grow-only device block carved into the run's arrays
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  size_t scan_tmp = 0; int64_t scan_n = -1;
+  std::vector<uint8_t> h_image; std::vector<int64_t> h_off, h_in_off; std::vector<uint32_t> h_status;
+};
+
+namespace {
+thread_local std::string g_derr;
+
+void do_deflate_run(snf_deflate* z, const uint8_t* data, int64_t len, const uint32_t* member_len, int64_t n, snf_deflate_result_t* out) {
+  if (!out || len < 0 || n < 0 || (len && !data) || (n && !member_len)) snf::fail("snf_deflate_run: null argument");
+  if (n >= (1ll << 31) / 2) snf::fail("snf_deflate_run: too many members for one run");
+  z->h_in_off.assign((size_t)n + 1, 0);
+  int64_t total = 0, bound = 0;
+  for (int64_t m = 0; m < n; m++) {
+    if (member_len[m] > DZ_MAX) snf::fail("snf_deflate_run: member " + std::to_string(m) + " has " + std::to_string(member_len[m]) + " bytes, a BGZF member takes 65280 (0xff00) at most");
+    z->h_in_off[(size_t)m] = total;
+    total += member_len[m]; bound += (int64_t)member_len[m] + 31;
+  }
+  z->h_in_off[(size_t)n] = total;
+  if (total != len) snf::fail("snf_deflate_run: the member lengths add up to " + std::to_string((long long)total) + ", the data has " + std::to_string((long long)len) + " bytes");
+  const DeflateKnobs k;
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(n, k.grid_cap));
+  const size_t N1 = (size_t)n + 1;
+  if (z->scan_n != n) {
+    size_t need = 0;
+    SNF_HIP(rocprim::exclusive_scan(nullptr, need, (const uint32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+    z->scan_tmp = need; z->scan_n = n;
+  }
+  uint8_t *d_in = nullptr, *d_slots = nullptr, *d_image = nullptr; int64_t *d_in_off = nullptr, *d_off = nullptr;
+  uint32_t *d_size = nullptr, *d_status = nullptr, *d_tok = nullptr; void* d_tmp = nullptr;
+  XSlab& s = z->slab;
+  s.measure();
+  for (int pass = 0; pass < 2; pass++) {      // measure, then carve
+    d_in = s.take<uint8_t>((size_t)len, 32);
+    d_in_off = s.take<int64_t>(N1);
+    d_slots = s.take<uint8_t>((size_t)n * DZ_SLOT);
+    d_size = s.take<uint32_t>(N1);
+    d_status = s.take<uint32_t>(N1);
+    d_tok = s.take<uint32_t>((size_t)len);
+    d_off = s.take<int64_t>(N1);
+    d_image = s.take<uint8_t>((size_t)bound, 16);
+    d_tmp = s.take<uint8_t>(z->scan_tmp ? z->scan_tmp : 1);
+    if (pass == 0) s.reserve();
+  }
+  x_h2d(d_in, data, (size_t)len);
+  x_h2d(d_in_off, z->h_in_off.data(), N1 * 8);
+  SNF_HIP(hipMemset(d_size + n, 0, 4));
+  for (hipEvent_t& e : z->ev) if (!e) SNF_HIP(hipEventCreate(&e));
+  SNF_HIP(hipEventRecord(z->ev[0], 0));
+  if (n) {
+    const DeflateView v{d_in, d_in_off, d_slots, d_size, d_status, d_tok, (uint32_t)k.max_bits};
+    hipLaunchKernelGGL(deflate_member, dim3((unsigned)grid), dim3(DZ_WG), 0, 0, v, n);
+    SNF_HIP(hipGetLastError());
+  }
+  size_t need = z->scan_tmp;
+  SNF_HIP(rocprim::exclusive_scan(d_tmp, need, (const uint32_t*)d_size, d_off, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  if (n) {
+    const PackView pv{d_slots, d_size, d_off, d_image};
+    hipLaunchKernelGGL(deflate_pack, dim3((unsigned)std::min<int64_t>(n, 1 << 16)), dim3(256), 0, 0, pv, n);
+    SNF_HIP(hipGetLastError());
+  }
+  SNF_HIP(hipEventRecord(z->ev[1], 0));
+  z->h_off.assign(N1, 0); z->h_status.assign(N1, 0);
+  x_d2h(z->h_off.data(), d_off, N1 * 8);
+  x_d2h(z->h_status.data(), d_status, (size_t)n * 4);
+  for (int64_t m = 0; m < n; m++) if (z->h_status[(size_t)m]) snf::fail("deflate member " + std::to_string(m) + ": the coded size differs from the size the histograms gave");
+  const int64_t image_len = z->h_off[(size_t)n];
+  if (image_len < 0 || image_len > bound) snf::fail("snf_deflate_run: member sizes out of range");
+  z->h_image.resize((size_t)image_len + 1);
+  x_d2h(z->h_image.data(), d_image, (size_t)image_len);
+  SNF_HIP(hipDeviceSynchronize());
+  snf_deflate_result_t r{};
+  SNF_HIP(hipEventElapsedTime(&r.ms_kernel, z->ev[0], z->ev[1]));
+  r.image = z->h_image.data(); r.image_len = image_len; r.member_off = z->h_off.data(); r.n_members = n;
+  *out = r;
+}
+}  // namespace
+
+extern "C" {
+const char* snf_deflate_last_error(void) { return g_derr.c_str(); }
+int snf_deflate_create(int device, snf_deflate_t** out) {
+  if (!out) { g_derr = "snf_deflate_create: null argument"; return 1; }
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { g_derr = "no HIP device: the deflate kernels need a gfx950 GPU (there is no CPU fallback)"; return 1; }
+  if (device < 0 || device >= nd) { g_derr = "device index out of range"; return 1; }
+  if (hipSetDevice(device) != hipSuccess) { g_derr = "hipSetDevice failed"; return 1; }
+  snf_deflate* z = new snf_deflate();
+  z->device = device;
+  *out = z;
+  return 0;
+}
+int snf_deflate_run(snf_deflate_t* z, const uint8_t* data, int64_t len, const uint32_t* member_len, int64_t n_members, snf_deflate_result_t* out) {
+  if (!z) { g_derr = "null handle"; return 1; }
+  if (hipSetDevice(z->device) != hipSuccess) { g_derr = "hipSetDevice failed"; return 1; }
+  try { do_deflate_run(z, data, len, member_len, n_members, out); }
+  catch (const snf::Error& e) { g_derr = e.msg; return 1; }
+  catch (const std::exception& e) { g_derr = e.what(); return 1; }
+  return 0;
+}
+void snf_deflate_destroy(snf_deflate_t* z) {
+  if (!z) return;
+  z->slab.release();
+  for (hipEvent_t e : z->ev) if (e) (void)hipEventDestroy(e);
   delete z;
 }
 }

@@ -104,6 +104,13 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.snf_bai_last_error.restype = C.c_char_p
     for f in ("snf_extract_attach_device", "snf_bgzf_create", "snf_bgzf_inflate", "snf_bgzf_result", "snf_bgzf_read_stream"):
         getattr(lib, f).restype = C.c_int
+    lib.snf_deflate_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.snf_deflate_run.argtypes = [vp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(abi.snf_deflate_result_t)]
+    lib.snf_deflate_destroy.argtypes = [vp]
+    lib.snf_deflate_destroy.restype = None
+    lib.snf_deflate_last_error.restype = C.c_char_p
+    for f in ("snf_deflate_create", "snf_deflate_run"):
+        getattr(lib, f).restype = C.c_int
     lib.snf_batch_pass.argtypes = [vp]
     lib.snf_batch_open.argtypes = [C.POINTER(abi.snf_config_t), C.c_int, C.POINTER(abi.snf_task_input_t), C.c_int32, C.c_int, C.POINTER(vp)]
     for f in ("snf_batch_open", "snf_batch_pass", "snf_batch_create", "snf_batch_add_task", "snf_batch_upload", "snf_batch_call_candidates",

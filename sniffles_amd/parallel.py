@@ -289,7 +289,7 @@ class CallTask(Task):
         sv.apply_final(calls, res, ti, finalize=True)
         return calls
 
-    def write_snf_part(self, svcandidates, snf_filename: str):
+    def write_snf_part(self, svcandidates, snf_filename: str, deflater=None):
         """The SNF tail of CallTask.execute (parallel.py:278-295): the task's candidates (after finalize_candidates) go
         into 100-kb blocks with their downsampled coverage and are written as a part file; the returned record is what
         `SNFile.add_result` / `write_results` consume."""
@@ -299,7 +299,7 @@ class CallTask(Task):
             for cand in svcandidates:
                 out.store(cand)
             out.annotate_block_coverages(self.lead_provider)
-            out.write_and_index()
+            out.write_and_index(deflater)      # (a bgzfout.DeflateDevice: the blocks through the GPU; None: gzip.compress)
         return snf.SNFPart(task_id=self.id, contig=self.contig, snf_filename=snf_filename, snf_index=out.get_index(),
                            snf_total_length=out.get_total_length(), snf_candidate_count=len(svcandidates),
                            coverage_average_total=self.coverage_average_total)

@@ -157,7 +157,7 @@ class _ContigInput:
             self.recs.close()
 
 
-def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None, tandem_repeats=None, device: int = 0, objects: bool = True, reference=None) -> SampleResult:
+def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None, tandem_repeats=None, device: int = 0, objects: bool = True, reference=None, snf_deflater=None) -> SampleResult:
     """`records`: `bam.read_bam(path)`, `bam.read_bam_device(path)` or `bam.open_indexed(path)` (only the contigs that are processed
     are read, through the index, one at a time).  `tandem_repeats`: {contig: [(start, end), ...]} (already padded, util.py:121-144).
     Writes the VCF to `vcf_handle` and / or the SNF to `snf_path` (CallTask.execute switches QC filtering off for the
@@ -165,7 +165,9 @@ def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None,
     `objects=False`: VCF only, formatted straight from the record table (vcf.VCF.write_records) - the same text, no `SVCall`
     objects (`SampleResult.calls` stays empty); falls back to the object path when a reference FASTA is attached.
     `reference` / `config.reference`: the reference FASTA (see `open_reference`) - with it the coverage of every task is masked
-    where the reference base is 'N' (`_mask_N_coverage`, leadprov.py:420-443, 470) and the writer resolves REF / ALT."""
+    where the reference base is 'N' (`_mask_N_coverage`, leadprov.py:420-443, 470) and the writer resolves REF / ALT.
+    `snf_deflater`: a `bgzfout.DeflateDevice` - the SNF blocks are compressed on the GPU (default: `gzip.compress` on this thread).
+    `vcf_handle` may be a `bgzfout.VcfGzWriter`: the `.vcf.gz` + `.tbi` the reference makes for `--vcf out.vcf.gz`."""
     total_mapped = _total_mapped(records)
     config.task_read_id_offset_mult = 10 ** 9 if total_mapped == 0 else 10 ** math.ceil(math.log(total_mapped) + 1)
     config.snf = snf_path
@@ -224,7 +226,7 @@ def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None,
                 calls = sorted(calls, key=lambda c: c.pos)
             out.read_count += info.read_count
             if snf_out is not None:
-                snf_out.add_result(task.write_snf_part(cands, f"{snf_path}.tmp_{task_id}.snf"))
+                snf_out.add_result(task.write_snf_part(cands, f"{snf_path}.tmp_{task_id}.snf", snf_deflater))
         finally:
             task.close()
             extractor.close()

@@ -288,9 +288,27 @@ class SNFileBase:
     def unserialize_block(self, data: bytes):
         return _Unpickler(io.BytesIO(data)).load()
 
-    def write_and_index(self):
+    def write_and_index(self, deflater=None):
+        """`deflater`: a bgzfout.DeflateDevice - all blocks of the part are compressed in one run on the GPU, each as a run of
+        BGZF members of 0xff00 bytes (a concatenation of gzip members: what `gzip.decompress` of the indexed range reads);
+        None: `gzip.compress` per block, as the reference."""
         out = self._io.need()
-        for block_id in sorted(self.blocks):
+        ids = sorted(self.blocks)
+        if deflater is not None and ids:
+            from .bgzfout import cut_members
+            raw = [self.serialize_block(block_id) for block_id in ids]
+            cuts = [cut_members(len(r)) for r in raw]
+            image, off = deflater.compress(b"".join(raw), [c for cut in cuts for c in cut])
+            k = 0
+            for block_id, cut in zip(ids, cuts):
+                a, b = int(off[k]), int(off[k + len(cut)])
+                k += len(cut)
+                out.write(image[a:b])
+                self._index[block_id] = (self.total_length, b - a)
+                self.total_length += b - a
+            self._io.done()
+            return
+        for block_id in ids:
             member = gzip.compress(self.serialize_block(block_id))
             out.write(member)
             self._index[block_id] = (self.total_length, len(member))
