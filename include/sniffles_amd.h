@@ -856,6 +856,70 @@ const char* snf_deflate_last_error(void);
  * The extraction does not own the attached memory.  A `device` other than the handle's is refused. */
 int snf_extract_attach_device(snf_extract_t* x, const snf_extract_input_t* in, const uint32_t* heads, int device);
 
+/* -----------------------------------------------------------------------------------------------------------------
+ * The reference FASTA resident on the device (csrc/snf_fasta.h): the whole text as one buffer in HBM, its `.fai` table,
+ * the runs of 'N' of a base range (`_mask_N_coverage`, leadprov.py:420-443) and batched base fetches (the VCF writer's
+ * REF / ALT, vcf.py:302-342).  The reference's counterpart is pysam.FastaFile; sniffles_amd/fasta.py FastaFile is the host
+ * form of the same rules.  Text offsets are 64-bit, base coordinates inside a contig 32-bit.  Additive to version 5.
+ * SNF_FASTA_GRID is read at every snf_fasta_index / snf_fasta_nruns / snf_fasta_fetch.  Results are library-owned until the
+ * next call on the handle.  CRC-32 of BGZF members is not checked, as in snf_bgzf_inflate.
+ * ----------------------------------------------------------------------------------------------------------------- */
+typedef struct snf_fasta_record {   /* one header line ('>' at byte 0 or behind a '\n') and the span up to the next one */
+  int64_t header_start, header_end; /* the header line [start, end): end is its '\n', or text_len */
+  int64_t line_start, line_end;     /* the first sequence line: header_end + 1 and its '\n' (or text_len); empty record: line_start >= span_end */
+  int64_t span_end;                 /* the next header line's start, or text_len */
+  int64_t n_newline, n_cr;          /* '\n' and line-end '\r' (in front of a '\n' or of the end of the text) in [line_start, span_end) */
+  int32_t line_cr, _pad;            /* the first sequence line ends in '\r' */
+} snf_fasta_record_t;
+
+typedef struct snf_fasta_index_result {
+  int64_t n_records, text_len;
+  const snf_fasta_record_t* rec;    /* host, n_records */
+  const uint8_t* headers;           /* host: the header lines ('>' included) one behind the other */
+  const int64_t* header_off;        /* host, n_records + 1 */
+  float ms_kernel, _pad;            /* HIP events around the count pass, the scans, the emit pass and fa_lines */
+} snf_fasta_index_result_t;
+
+typedef struct snf_fasta_runs {
+  int64_t n_runs;
+  const int32_t *start, *end;       /* host, n_runs: sorted, disjoint [start, end) in contig coordinates */
+  int32_t regular, _pad;            /* 0: the text range did not hold hi - lo bases (lines of another width than the index says); no runs returned */
+  float ms_kernel, _pad2;
+} snf_fasta_runs_t;
+
+enum snf_fasta_status { SNF_FASTA_OK = 0, SNF_FASTA_START_NEGATIVE = 1, SNF_FASTA_START_ABOVE_END = 2, SNF_FASTA_KEY_ERROR = 3 };
+
+typedef struct snf_fasta_fetch {
+  int64_t n;
+  const uint8_t* pool;              /* host: the bases of every query, line ends taken out, one behind the other */
+  const int64_t* off;               /* host, n + 1: exclusive sum of the clipped lengths */
+  const int32_t* status;            /* host, n: snf_fasta_status (pysam's fetch: end clipped to the length; start < 0 and start > end with
+                                       start < length are its ValueErrors; start >= length is empty; an unknown contig its KeyError) */
+  const int32_t* n_count;           /* host, n: bytes 'N' among the query's bases */
+  float ms_kernel, _pad;
+} snf_fasta_fetch_t;
+
+typedef struct snf_fasta snf_fasta_t;
+/* `capacity`: bytes of text the handle will hold; "reference of <capacity> bytes does not fit device <device>" when they cannot be allocated. */
+int snf_fasta_create(int device, int64_t capacity, snf_fasta_t** out);
+/* Both append behind what the handle holds (a plain file: one call; a bgzip file: a call per run of members).  `members`: as for
+ * snf_bgzf_inflate, out_off the exclusive sum of ISIZE within the run; a malformed member fails with the inflate's message. */
+int snf_fasta_load_text(snf_fasta_t* f, const uint8_t* bytes, int64_t len);
+int snf_fasta_load_bgzf(snf_fasta_t* f, const uint8_t* compressed, int64_t compressed_len, const snf_bgzf_member_t* members,
+                        int64_t n_members, float* ms_inflate);
+/* The header lines of the text; the caller turns them into the `.fai` table and hands it back (or the table of a `.fai` file). */
+int snf_fasta_index(snf_fasta_t* f, snf_fasta_index_result_t* out);
+/* Per contig: bases, text offset of the first base, bases and bytes of a line.  A contig whose last base lies behind the text is refused. */
+int snf_fasta_set_index(snf_fasta_t* f, int64_t n_contigs, const int64_t* length, const int64_t* offset, const int64_t* line_bases,
+                        const int64_t* line_width);
+/* The runs of the byte 'N' (upper case only) in the bases [lo, hi) of contig number `contig`, 0 <= lo <= hi <= length. */
+int snf_fasta_nruns(snf_fasta_t* f, int64_t contig, int32_t lo, int32_t hi, snf_fasta_runs_t* out);
+/* `n` queries [start, end) on one contig; `contig` -1: a name the index does not have (SNF_FASTA_KEY_ERROR for every query). */
+int snf_fasta_fetch(snf_fasta_t* f, int64_t contig, int64_t n, const int64_t* start, const int64_t* end, snf_fasta_fetch_t* out);
+int snf_fasta_read_text(snf_fasta_t* f, int64_t off, int64_t len, uint8_t* dst);   /* text bytes back to the host (tests) */
+void snf_fasta_destroy(snf_fasta_t* f);
+const char* snf_fasta_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -470,6 +470,35 @@ class snf_deflate_result_t(C.Structure):
                 ("ms_kernel", C.c_float), ("_pad", C.c_float)]
 
 
+# ---- reference FASTA on the device (snf_fasta_*, csrc/snf_fasta.h)
+class snf_fasta_record_t(C.Structure):
+    _fields_ = [("header_start", i64), ("header_end", i64), ("line_start", i64), ("line_end", i64), ("span_end", i64),
+                ("n_newline", i64), ("n_cr", i64), ("line_cr", i32), ("_pad", i32)]
+
+
+FASTA_RECORD_DTYPE = np.dtype([(n, "<i8") for n in ("header_start", "header_end", "line_start", "line_end", "span_end", "n_newline", "n_cr")] +
+                              [("line_cr", "<i4"), ("_pad", "<i4")])
+assert FASTA_RECORD_DTYPE.itemsize == C.sizeof(snf_fasta_record_t) == 64
+
+
+class snf_fasta_index_result_t(C.Structure):
+    _fields_ = [("n_records", i64), ("text_len", i64), ("rec", C.POINTER(snf_fasta_record_t)), ("headers", u8p),
+                ("header_off", C.POINTER(C.c_int64)), ("ms_kernel", C.c_float), ("_pad", C.c_float)]
+
+
+class snf_fasta_runs_t(C.Structure):
+    _fields_ = [("n_runs", i64), ("start", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)), ("regular", i32), ("_pad", i32),
+                ("ms_kernel", C.c_float), ("_pad2", C.c_float)]
+
+
+FASTA_OK, FASTA_START_NEGATIVE, FASTA_START_ABOVE_END, FASTA_KEY_ERROR = 0, 1, 2, 3
+
+
+class snf_fasta_fetch_t(C.Structure):
+    _fields_ = [("n", i64), ("pool", u8p), ("off", C.POINTER(C.c_int64)), ("status", C.POINTER(C.c_int32)),
+                ("n_count", C.POINTER(C.c_int32)), ("ms_kernel", C.c_float), ("_pad", C.c_float)]
+
+
 def extract_config_struct(cfg) -> snf_extract_config_t:
     """`cfg`: anything with the SnifflesConfig attribute names extraction reads (config.py:190-215, 507-617)."""
     g = lambda name, default: getattr(cfg, name, default)

@@ -1021,6 +1021,7 @@ SNF_HD void x_totals_body(int64_t i, const ExView& v) {
 #include "snf_bgzf.h"
 #include "snf_bamindex.h"
 #include "snf_deflate.h"
+#include "snf_fasta.h"
 using namespace snf;
 SNF_KERNEL(x_count, ExView)
 SNF_KERNEL(x_emit, ExView)
@@ -1898,5 +1899,309 @@ void snf_deflate_destroy(snf_deflate_t* z) {
   z->slab.release();
   for (hipEvent_t e : z->ev) if (e) (void)hipEventDestroy(e);
   delete z;
+}
+}
+
+// ============================================================================= reference FASTA in HBM: host side ====
+struct snf_fasta {
+  int device = 0;
+  uint8_t* d_text = nullptr; int64_t cap = 0, len = 0;      // cap + 64 bytes allocated
+  std::vector<void*> tmp;                                  // the device arrays of one call
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  std::vector<int64_t> c_len, c_off, c_lb, c_lw; bool have_index = false;
+  std::vector<snf_fasta_record_t> h_rec; std::vector<uint8_t> h_hdr; std::vector<int64_t> h_hdr_off;
+  std::vector<int32_t> h_rs, h_re;
+  std::vector<uint8_t> h_pool; std::vector<int64_t> h_off; std::vector<int32_t> h_status, h_ncount, h_qs, h_ql;
+};
+
+namespace {
+thread_local std::string g_ferr;
+
+unsigned fa_grid(int64_t items, const FastaKnobs& k) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, k.grid_cap)); }
+
+void fa_events(snf_fasta* f) { for (hipEvent_t& e : f->ev) if (!e) SNF_HIP(hipEventCreate(&e)); }
+
+void fa_room(snf_fasta* f, int64_t more) {
+  if (more < 0 || f->len + more > f->cap)
+    snf::fail("snf_fasta: " + std::to_string((long long)more) + " more bytes behind " + std::to_string((long long)f->len) + " do not fit the " +
+              std::to_string((long long)f->cap) + " bytes the handle was created for");
+}
+void fa_appended(snf_fasta* f, int64_t more) {
+  f->len += more;
+  SNF_HIP(hipMemset(f->d_text + f->len, 0, 64));
+  f->have_index = false;
+}
+
+void do_fasta_load_bgzf(snf_fasta* f, const uint8_t* comp, int64_t comp_len, const snf_bgzf_member_t* mem, int64_t n_mem, float* ms) {
+  if (comp_len < 0 || n_mem < 0 || (comp_len && !comp) || (n_mem && !mem)) snf::fail("snf_fasta_load_bgzf: null argument");
+  int64_t total = 0;
+  std::vector<snf_bgzf_member_t> abs((size_t)n_mem);
+  for (int64_t m = 0; m < n_mem; m++) {
+    const snf_bgzf_member_t& b = mem[m];
+    if (b.payload_off < 0 || b.payload_off + (int64_t)b.payload_len > comp_len) snf::fail("BGZF member " + std::to_string(m) + ": payload outside the compressed bytes");
+    if (b.isize > BZ_WIN) snf::fail("BGZF member " + std::to_string(m) + ": ISIZE above 65536");
+    if (b.out_off != total) snf::fail("BGZF member " + std::to_string(m) + ": out_off is not the exclusive sum of ISIZE");
+    abs[(size_t)m] = b; abs[(size_t)m].out_off = f->len + total;      // the kernel writes at text + out_off: the run is appended
+    total += b.isize;
+  }
+  fa_room(f, total);
+  const BgzfKnobs k;
+  x_release(f->tmp);
+  uint8_t* d_comp = x_up(f->tmp, comp, (size_t)comp_len, 16);
+  snf_bgzf_member_t* d_mem = x_up(f->tmp, abs.data(), (size_t)n_mem);
+  uint32_t* d_status = x_alloc<uint32_t>(f->tmp, (size_t)n_mem);
+  fa_events(f);
+  BgzfView bv{d_comp, d_mem, n_mem, f->d_text, d_status};
+  SNF_HIP(hipEventRecord(f->ev[0], 0));
+  if (n_mem) {
+    if (k.thread_form) hipLaunchKernelGGL(bgzf_inflate_thread, dim3((unsigned)((n_mem + 63) / 64)), dim3(64), 0, 0, bv, n_mem);
+    else hipLaunchKernelGGL(bgzf_inflate_wave, dim3((unsigned)std::min<int64_t>(n_mem, k.grid_cap)), dim3(64), 0, 0, bv, n_mem);
+    SNF_HIP(hipGetLastError());
+  }
+  SNF_HIP(hipEventRecord(f->ev[1], 0));
+  std::vector<uint32_t> status((size_t)n_mem);
+  x_d2h(status.data(), d_status, (size_t)n_mem * 4);
+  SNF_HIP(hipDeviceSynchronize());
+  x_release(f->tmp);
+  for (int64_t m = 0; m < n_mem; m++)
+    if (status[(size_t)m]) snf::fail("BGZF member " + std::to_string(m) + ": " + BZ_TEXT[status[(size_t)m] < 8 ? status[(size_t)m] : 4]);
+  if (ms) SNF_HIP(hipEventElapsedTime(ms, f->ev[0], f->ev[1]));
+  fa_appended(f, total);
+}
+
+void do_fasta_index(snf_fasta* f, snf_fasta_index_result_t* out) {
+  if (!out) snf::fail("snf_fasta_index: null argument");
+  const FastaKnobs k;
+  x_release(f->tmp);
+  std::vector<void*>& pool = f->tmp;
+  const int64_t n = f->len, n_chunks = (n + FA_CHUNK - 1) / FA_CHUNK;
+  const size_t N1 = (size_t)n_chunks + 1;
+  FaIndexView v{};
+  v.text = f->d_text; v.n = n; v.n_chunks = n_chunks;
+  v.c_nl = x_alloc<uint32_t>(pool, N1); v.c_cr = x_alloc<uint32_t>(pool, N1); v.c_hdr = x_alloc<uint32_t>(pool, N1);
+  int64_t* p_nl = x_alloc<int64_t>(pool, N1); int64_t* p_cr = x_alloc<int64_t>(pool, N1); int64_t* p_hdr = x_alloc<int64_t>(pool, N1);
+  v.p_nl = p_nl; v.p_cr = p_cr; v.p_hdr = p_hdr;
+  SNF_HIP(hipMemset(v.c_nl + n_chunks, 0, 4)); SNF_HIP(hipMemset(v.c_cr + n_chunks, 0, 4)); SNF_HIP(hipMemset(v.c_hdr + n_chunks, 0, 4));
+  size_t need = 0;
+  SNF_HIP(rocprim::exclusive_scan(nullptr, need, (const uint32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  void* scan_tmp = x_alloc<uint8_t>(pool, need);
+  fa_events(f);
+  const unsigned grid = fa_grid(n_chunks, k);
+  SNF_HIP(hipEventRecord(f->ev[0], 0));
+  if (n_chunks) { hipLaunchKernelGGL(fa_index<false>, dim3(grid), dim3(FA_WG), 0, 0, v); SNF_HIP(hipGetLastError()); }
+  SNF_HIP(rocprim::exclusive_scan(scan_tmp, need, (const uint32_t*)v.c_nl, p_nl, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  SNF_HIP(rocprim::exclusive_scan(scan_tmp, need, (const uint32_t*)v.c_cr, p_cr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  SNF_HIP(rocprim::exclusive_scan(scan_tmp, need, (const uint32_t*)v.c_hdr, p_hdr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  int64_t tot_nl = 0, tot_cr = 0, n_rec = 0;
+  x_d2h(&tot_nl, p_nl + n_chunks, 8); x_d2h(&tot_cr, p_cr + n_chunks, 8); x_d2h(&n_rec, p_hdr + n_chunks, 8);
+  std::vector<FaRec> rec((size_t)n_rec + 1);
+  if (n_rec) {
+    v.rec = x_alloc<FaRec>(pool, (size_t)n_rec); v.n_rec = n_rec;
+    SNF_HIP(hipMemset(v.rec, 0, (size_t)n_rec * sizeof(FaRec)));
+    hipLaunchKernelGGL(fa_index<true>, dim3(grid), dim3(FA_WG), 0, 0, v); SNF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fa_lines, dim3(fa_grid(n_rec, k)), dim3(64), 0, 0, v); SNF_HIP(hipGetLastError());
+  }
+  SNF_HIP(hipEventRecord(f->ev[1], 0));
+  x_d2h(rec.data(), v.rec, (size_t)n_rec * sizeof(FaRec));
+  // the header lines (names), then the counts of every record's span: what lies between its header line and the next one
+  f->h_rec.assign((size_t)n_rec + 1, snf_fasta_record_t{}); f->h_hdr_off.assign((size_t)n_rec + 1, 0);
+  int64_t hbytes = 0;
+  for (int64_t r = 0; r < n_rec; r++) {
+    const FaRec& a = rec[(size_t)r];
+    if (a.pos < 0 || a.hdr_end <= a.pos || a.hdr_end > n || a.line_end > n) snf::fail("snf_fasta_index: header table malformed");
+    f->h_hdr_off[(size_t)r] = hbytes; hbytes += a.hdr_end - a.pos;
+  }
+  f->h_hdr_off[(size_t)n_rec] = hbytes;
+  f->h_hdr.assign((size_t)hbytes + 1, 0);
+  for (int64_t r = 0; r < n_rec; r++) x_d2h(f->h_hdr.data() + f->h_hdr_off[(size_t)r], f->d_text + rec[(size_t)r].pos, (size_t)(rec[(size_t)r].hdr_end - rec[(size_t)r].pos));
+  for (int64_t r = 0; r < n_rec; r++) {
+    const FaRec& a = rec[(size_t)r];
+    const bool last = r + 1 == n_rec;
+    const int64_t nl_next = last ? tot_nl : rec[(size_t)r + 1].nl_before, cr_next = last ? tot_cr : rec[(size_t)r + 1].cr_before;
+    const bool hdr_nl = a.hdr_end < n, hdr_cr = f->h_hdr[(size_t)(f->h_hdr_off[(size_t)r + 1] - 1)] == 13;
+    snf_fasta_record_t& o = f->h_rec[(size_t)r];
+    o.header_start = a.pos; o.header_end = a.hdr_end; o.line_start = a.hdr_end + 1; o.line_end = a.line_end; o.line_cr = (int32_t)a.line_cr;
+    o.span_end = last ? n : rec[(size_t)r + 1].pos;
+    o.n_newline = nl_next - a.nl_before - (hdr_nl ? 1 : 0); o.n_cr = cr_next - a.cr_before - (hdr_cr ? 1 : 0);
+  }
+  SNF_HIP(hipDeviceSynchronize());
+  snf_fasta_index_result_t r{};
+  SNF_HIP(hipEventElapsedTime(&r.ms_kernel, f->ev[0], f->ev[1]));
+  r.n_records = n_rec; r.rec = f->h_rec.data(); r.headers = f->h_hdr.data(); r.header_off = f->h_hdr_off.data(); r.text_len = n;
+  x_release(pool);
+  *out = r;
+}
+
+void do_fasta_set_index(snf_fasta* f, int64_t n, const int64_t* length, const int64_t* offset, const int64_t* lb, const int64_t* lw) {
+  if (n < 0 || (n && (!length || !offset || !lb || !lw))) snf::fail("snf_fasta_set_index: null argument");
+  for (int64_t c = 0; c < n; c++) {
+    const std::string at = "snf_fasta_set_index: contig " + std::to_string((long long)c);
+    if (length[c] < 0 || length[c] >= (1ll << 31)) snf::fail(at + " has " + std::to_string((long long)length[c]) + " bases, base coordinates are 32-bit");
+    if (lb[c] < 1 || lw[c] < lb[c] || lw[c] >= (1ll << 31)) snf::fail(at + ": line of " + std::to_string((long long)lb[c]) + " bases in " + std::to_string((long long)lw[c]) + " bytes");
+    if (offset[c] < 0) snf::fail(at + ": negative offset");
+    if (length[c]) {
+      const int64_t lastb = offset[c] + ((length[c] - 1) / lb[c]) * lw[c] + (length[c] - 1) % lb[c];
+      if (lastb >= f->len) snf::fail(at + ": its last base lies at byte " + std::to_string((long long)lastb) + ", the text has " + std::to_string((long long)f->len) + " bytes (an index of another file?)");
+    }
+  }
+  f->c_len.assign(length, length + n); f->c_off.assign(offset, offset + n); f->c_lb.assign(lb, lb + n); f->c_lw.assign(lw, lw + n);
+  f->have_index = true;
+}
+
+void fa_contig(snf_fasta* f, int64_t contig, const char* who) {
+  if (!f->have_index) snf::fail(std::string(who) + " before snf_fasta_set_index");
+  if (contig < 0 || contig >= (int64_t)f->c_len.size()) snf::fail(std::string(who) + ": contig index out of range");
+}
+
+void do_fasta_nruns(snf_fasta* f, int64_t contig, int32_t lo, int32_t hi, snf_fasta_runs_t* out) {
+  if (!out) snf::fail("snf_fasta_nruns: null argument");
+  fa_contig(f, contig, "snf_fasta_nruns");
+  const int64_t length = f->c_len[(size_t)contig], offset = f->c_off[(size_t)contig], lb = f->c_lb[(size_t)contig], lw = f->c_lw[(size_t)contig];
+  if (lo < 0 || hi < lo || hi > length) snf::fail("snf_fasta_nruns: [" + std::to_string(lo) + ", " + std::to_string(hi) + ") is not a clipped range of a contig of " + std::to_string((long long)length) + " bases");
+  snf_fasta_runs_t r{};
+  f->h_rs.assign(1, 0); f->h_re.assign(1, 0);
+  r.start = f->h_rs.data(); r.end = f->h_re.data(); r.regular = 1;
+  if (hi == lo) { *out = r; return; }
+  const FastaKnobs k;
+  x_release(f->tmp);
+  std::vector<void*>& pool = f->tmp;
+  FaRunsView v{};
+  v.text = f->d_text; v.lo = lo;
+  v.b0 = offset + (lo / lb) * lw + lo % lb; v.b1 = offset + ((hi - 1) / lb) * lw + (hi - 1) % lb + 1;      // < f->len: checked by set_index
+  v.a0 = v.b0 & ~(int64_t)(FA_VEC - 1);
+  v.n_chunks = (v.b1 - v.a0 + FA_CHUNK - 1) / FA_CHUNK;
+  const size_t N1 = (size_t)v.n_chunks + 1;
+  v.c_se = x_alloc<unsigned long long>(pool, N1); v.c_le = x_alloc<uint32_t>(pool, N1);
+  unsigned long long* p_se = x_alloc<unsigned long long>(pool, N1); int64_t* p_le = x_alloc<int64_t>(pool, N1);
+  v.p_se = p_se; v.p_le = p_le;
+  SNF_HIP(hipMemset(v.c_se + v.n_chunks, 0, 8)); SNF_HIP(hipMemset(v.c_le + v.n_chunks, 0, 4));
+  size_t need_a = 0, need_b = 0;
+  SNF_HIP(rocprim::exclusive_scan(nullptr, need_a, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull, N1, rocprim::plus<unsigned long long>(), 0));
+  SNF_HIP(rocprim::exclusive_scan(nullptr, need_b, (const uint32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  void* tmp_a = x_alloc<uint8_t>(pool, need_a); void* tmp_b = x_alloc<uint8_t>(pool, need_b);
+  fa_events(f);
+  const unsigned grid = fa_grid(v.n_chunks, k);
+  SNF_HIP(hipEventRecord(f->ev[0], 0));
+  hipLaunchKernelGGL(fa_nruns<false>, dim3(grid), dim3(FA_WG), 0, 0, v); SNF_HIP(hipGetLastError());
+  SNF_HIP(rocprim::exclusive_scan(tmp_a, need_a, (const unsigned long long*)v.c_se, p_se, 0ull, N1, rocprim::plus<unsigned long long>(), 0));
+  SNF_HIP(rocprim::exclusive_scan(tmp_b, need_b, (const uint32_t*)v.c_le, p_le, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  unsigned long long tot_se = 0; int64_t tot_le = 0;
+  x_d2h(&tot_se, p_se + v.n_chunks, 8); x_d2h(&tot_le, p_le + v.n_chunks, 8);
+  const int64_t n_runs = (int64_t)(tot_se & 0xffffffffull);
+  if ((int64_t)(tot_se >> 32) != n_runs) snf::fail("snf_fasta_nruns: opens and closes differ");
+  r.regular = (v.b1 - v.b0) - tot_le == (int64_t)hi - lo ? 1 : 0;      // else: lines of another width than the index says - the runs are not returned
+  if (n_runs && r.regular) {
+    v.start = x_alloc<int32_t>(pool, (size_t)n_runs); v.end = x_alloc<int32_t>(pool, (size_t)n_runs); v.n_runs = n_runs;
+    hipLaunchKernelGGL(fa_nruns<true>, dim3(grid), dim3(FA_WG), 0, 0, v); SNF_HIP(hipGetLastError());
+  }
+  SNF_HIP(hipEventRecord(f->ev[1], 0));
+  if (n_runs && r.regular) {
+    f->h_rs.assign((size_t)n_runs, 0); f->h_re.assign((size_t)n_runs, 0);
+    x_d2h(f->h_rs.data(), v.start, (size_t)n_runs * 4); x_d2h(f->h_re.data(), v.end, (size_t)n_runs * 4);
+    r.n_runs = n_runs; r.start = f->h_rs.data(); r.end = f->h_re.data();
+  }
+  SNF_HIP(hipDeviceSynchronize());
+  SNF_HIP(hipEventElapsedTime(&r.ms_kernel, f->ev[0], f->ev[1]));
+  x_release(pool);
+  *out = r;
+}
+
+void do_fasta_fetch(snf_fasta* f, int64_t contig, int64_t n, const int64_t* start, const int64_t* end, snf_fasta_fetch_t* out) {
+  if (!out || n < 0 || (n && (!start || !end))) snf::fail("snf_fasta_fetch: null argument");
+  if (!f->have_index) snf::fail("snf_fasta_fetch before snf_fasta_set_index");
+  if (contig >= (int64_t)f->c_len.size()) snf::fail("snf_fasta_fetch: contig index out of range");
+  const bool known = contig >= 0;
+  const int64_t length = known ? f->c_len[(size_t)contig] : 0;
+  f->h_off.assign((size_t)n + 1, 0); f->h_status.assign((size_t)n + 1, 0); f->h_ncount.assign((size_t)n + 1, 0);
+  f->h_qs.assign((size_t)n + 1, 0); f->h_ql.assign((size_t)n + 1, 0);
+  int64_t total = 0;
+  for (int64_t q = 0; q < n; q++) {      // FastaFile.fetch, statement for statement
+    int32_t st = SNF_FASTA_OK; int64_t len = 0;
+    const int64_t s = start[q], e = std::min(end[q], length);
+    if (!known) st = SNF_FASTA_KEY_ERROR;
+    else if (s < 0) st = SNF_FASTA_START_NEGATIVE;
+    else if (s > e) { if (s < length) st = SNF_FASTA_START_ABOVE_END; }
+    else len = e - s;
+    f->h_status[(size_t)q] = st; f->h_off[(size_t)q] = total; f->h_qs[(size_t)q] = (int32_t)(len ? s : 0); f->h_ql[(size_t)q] = (int32_t)len;
+    total += len;
+  }
+  f->h_off[(size_t)n] = total;
+  f->h_pool.assign((size_t)total + 1, 0);
+  snf_fasta_fetch_t r{};
+  if (total) {
+    const FastaKnobs k;
+    x_release(f->tmp);
+    std::vector<void*>& pool = f->tmp;
+    FaGatherView v{};
+    v.text = f->d_text; v.offset = f->c_off[(size_t)contig]; v.lb = (uint32_t)f->c_lb[(size_t)contig]; v.lw = (uint32_t)f->c_lw[(size_t)contig];
+    v.start = x_up(pool, f->h_qs.data(), (size_t)n); v.len = x_up(pool, f->h_ql.data(), (size_t)n); v.off = x_up(pool, f->h_off.data(), (size_t)n + 1);
+    v.pool = x_alloc<uint8_t>(pool, (size_t)total); v.n_count = x_alloc<int32_t>(pool, (size_t)n);
+    fa_events(f);
+    SNF_HIP(hipEventRecord(f->ev[0], 0));
+    hipLaunchKernelGGL(fa_gather, dim3(fa_grid(n, k)), dim3(64), 0, 0, v, n); SNF_HIP(hipGetLastError());
+    SNF_HIP(hipEventRecord(f->ev[1], 0));
+    x_d2h(f->h_pool.data(), v.pool, (size_t)total); x_d2h(f->h_ncount.data(), v.n_count, (size_t)n * 4);
+    SNF_HIP(hipDeviceSynchronize());
+    SNF_HIP(hipEventElapsedTime(&r.ms_kernel, f->ev[0], f->ev[1]));
+    x_release(pool);
+  }
+  r.n = n; r.pool = f->h_pool.data(); r.off = f->h_off.data(); r.status = f->h_status.data(); r.n_count = f->h_ncount.data();
+  *out = r;
+}
+}  // namespace
+
+#define F_TRY(stmt)                                                    \
+  if (!f) { g_ferr = "null handle"; return 1; }                        \
+  if (hipSetDevice(f->device) != hipSuccess) { g_ferr = "hipSetDevice failed"; return 1; } \
+  try { stmt; }                                                        \
+  catch (const snf::Error& e) { g_ferr = e.msg; return 1; }            \
+  catch (const std::exception& e) { g_ferr = e.what(); return 1; }     \
+  return 0;
+
+extern "C" {
+const char* snf_fasta_last_error(void) { return g_ferr.c_str(); }
+int snf_fasta_create(int device, int64_t capacity, snf_fasta_t** out) {
+  if (!out || capacity < 0) { g_ferr = "snf_fasta_create: null argument"; return 1; }
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { g_ferr = "no HIP device: the FASTA kernels need a gfx950 GPU (there is no CPU fallback)"; return 1; }
+  if (device < 0 || device >= nd) { g_ferr = "device index out of range"; return 1; }
+  if (hipSetDevice(device) != hipSuccess) { g_ferr = "hipSetDevice failed"; return 1; }
+  void* p = nullptr;
+  if (hipMalloc(&p, (size_t)capacity + 64) != hipSuccess) {
+    (void)hipGetLastError();
+    g_ferr = "reference of " + std::to_string((long long)capacity) + " bytes does not fit device " + std::to_string(device);
+    return 1;
+  }
+  if (hipMemset(p, 0, (size_t)capacity + 64) != hipSuccess) { (void)hipFree(p); g_ferr = "hipMemset failed"; return 1; }
+  snf_fasta* f = new snf_fasta();
+  f->device = device; f->d_text = (uint8_t*)p; f->cap = capacity;
+  *out = f;
+  return 0;
+}
+int snf_fasta_load_text(snf_fasta_t* f, const uint8_t* bytes, int64_t len) {
+  F_TRY(if (len < 0 || (len && !bytes)) snf::fail("snf_fasta_load_text: null argument"); fa_room(f, len); x_h2d(f->d_text + f->len, bytes, (size_t)len); fa_appended(f, len))
+}
+int snf_fasta_load_bgzf(snf_fasta_t* f, const uint8_t* compressed, int64_t compressed_len, const snf_bgzf_member_t* members, int64_t n_members, float* ms_inflate) {
+  F_TRY(do_fasta_load_bgzf(f, compressed, compressed_len, members, n_members, ms_inflate))
+}
+int snf_fasta_index(snf_fasta_t* f, snf_fasta_index_result_t* out) { F_TRY(do_fasta_index(f, out)) }
+int snf_fasta_set_index(snf_fasta_t* f, int64_t n_contigs, const int64_t* length, const int64_t* offset, const int64_t* line_bases, const int64_t* line_width) {
+  F_TRY(do_fasta_set_index(f, n_contigs, length, offset, line_bases, line_width))
+}
+int snf_fasta_nruns(snf_fasta_t* f, int64_t contig, int32_t lo, int32_t hi, snf_fasta_runs_t* out) { F_TRY(do_fasta_nruns(f, contig, lo, hi, out)) }
+int snf_fasta_fetch(snf_fasta_t* f, int64_t contig, int64_t n, const int64_t* start, const int64_t* end, snf_fasta_fetch_t* out) {
+  F_TRY(do_fasta_fetch(f, contig, n, start, end, out))
+}
+int snf_fasta_read_text(snf_fasta_t* f, int64_t off, int64_t len, uint8_t* dst) {
+  F_TRY(if (len && !dst) snf::fail("snf_fasta_read_text: null argument");
+        if (off < 0 || len < 0 || off + len > f->len) snf::fail("snf_fasta_read_text: range outside the text");
+        x_d2h(dst, f->d_text + off, (size_t)len))
+}
+void snf_fasta_destroy(snf_fasta_t* f) {
+  if (!f) return;
+  x_release(f->tmp);
+  if (f->d_text) (void)hipFree(f->d_text);
+  for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
+  delete f;
 }
 }

@@ -9,7 +9,7 @@
 //                 here and is resolved where the data is known.
 //   ProcessKnobs  what configures state shared by all handles of the process (pacing, pools, arenas): once per process, at the
 //                 first use of process_knobs().
-//   ExtractKnobs / BgzfKnobs / BaiKnobs / DeflateKnobs / CombineKnobs   the entry points without a long-lived handle: constructed at the top of each call.
+//   ExtractKnobs / BgzfKnobs / BaiKnobs / DeflateKnobs / FastaKnobs / CombineKnobs   the entry points without a long-lived handle: constructed at the top of each call.
 // The parses are not uniform on purpose - each keeps the meaning its switch always had ("set at all", "atoi != 0", clamped, a
 // string compared).  Defaults are the product path; everything else exists for tests and measurements.
 #pragma once
@@ -126,6 +126,11 @@ struct DeflateKnobs {   // read at every snf_deflate_run
   int grid_cap = env_set("SNF_DEFLATE_GRID") ? env_pos("SNF_DEFLATE_GRID", 1) : (1 << 20);   // SNF_DEFLATE_GRID=n (at least 1), default 2^20: the deflate grid; beyond it a workgroup takes several members
   int max_bits = [] { const int v = env_int("SNF_DEFLATE_MAXBITS", 15); return v >= 9 && v <= 15 ? v : 15; }();   // SNF_DEFLATE_MAXBITS=9..15, default 15 (deflate's limit; anything
                                                      //   else: 15): longest literal/length or distance code - tests lower it, so that ordinary inputs reach the limiter
+};
+
+struct FastaKnobs {   // read at every snf_fasta_index / snf_fasta_nruns / snf_fasta_fetch
+  int grid_cap = env_set("SNF_FASTA_GRID") ? env_pos("SNF_FASTA_GRID", 1) : (1 << 20);   // SNF_FASTA_GRID=n (at least 1), default 2^20: the grids of fa_index / fa_nruns / fa_gather;
+                                                     //   beyond it a workgroup takes several chunks, a wave several queries
 };
 
 struct CombineKnobs {   // read at every snf_combine_resolve_batch

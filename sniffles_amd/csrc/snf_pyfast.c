@@ -1658,22 +1658,40 @@ done:
 /* ======================================================================================================================
  * vcf_records(): single-sample VCF lines straight from the record table (sniffles_amd/vcf.py::VCF.write_records): what
  * materialize + apply_final + VCF.write_call (vcf.py:216-350 of the reference) produce for the same records, without the
- * SVCall objects in between.  Serves the BAM -> VCF flow when no reference FASTA is attached and no SNF is written.
+ * SVCall objects in between.  Serves the BAM -> VCF flow when no SNF is written and the reference FASTA, if one is attached, is
+ * resident on the device (its bases come in as query tables).
  * ====================================================================================================================== */
 /* vcf_records(records: buffer, order: buffer int64 (record indices in output order), rnames: buffer uint32, alt_pool: buffer,
  *             qnames: list | None, ps_names: list | None, contig: str, task_id: int, contig_names: list | None,
  *             filters: list[str], opts: dict(id_prefix str, mosaic, mosaic_af_max, output_rnames, nm, phase, symbolic, minsvlen,
- *             genotype_format str, genotype_none str)) -> (bytes, records written) */
+ *             genotype_format str, genotype_none str)
+ *             [, ref: (del_idx int64[n], del_pool, del_off int64, del_status int32, del_n int32, base_pool, base_off int64[n + 1],
+ *                      base_status int32[n], max_unknown_pct float) - the bases a device-resident reference fetched; omitted: REF "N"])
+ *   -> (bytes, records written) */
 static PyObject* py_vcf_records(PyObject* self, PyObject* args) {
   PyObject *qnames, *ps_names, *contig, *contig_names, *filters, *opts;
   Py_buffer rec, ord, rn, pool;
   long long task_id;
-  if (!PyArg_ParseTuple(args, "y*y*y*y*OOULOO!O!", &rec, &ord, &rn, &pool, &qnames, &ps_names, &contig, &task_id, &contig_names,
-                        &PyList_Type, &filters, &PyDict_Type, &opts))
+  PyObject* refq = NULL;
+  if (!PyArg_ParseTuple(args, "y*y*y*y*OOULOO!O!|O", &rec, &ord, &rn, &pool, &qnames, &ps_names, &contig, &task_id, &contig_names,
+                        &PyList_Type, &filters, &PyDict_Type, &opts, &refq))
     return NULL;
   PyObject* ret = NULL;
   OutBuf b = {NULL, 0, 0};
   long long written = 0;
+  /* the reference bases the device fetched (fasta.DeviceFasta.fetch_many), per record of `order`: the deletion's query (del_idx: its
+   * number among the deletion queries, -1: none made) and the one-base query at max(0, pos - 1) */
+  Py_buffer q_didx, q_dpool, q_doff, q_dst, q_dn, q_opool, q_ooff, q_ost;
+  double max_unknown = 0.0;
+  int have_ref = 0;
+  if (refq && refq != Py_None) {
+    if (!PyTuple_Check(refq) || !PyArg_ParseTuple(refq, "y*y*y*y*y*y*y*y*d", &q_didx, &q_dpool, &q_doff, &q_dst, &q_dn, &q_opool, &q_ooff, &q_ost, &max_unknown)) {
+      if (!PyErr_Occurred()) PyErr_SetString(PyExc_TypeError, "vcf_records: the reference queries are a tuple");
+      PyBuffer_Release(&rec); PyBuffer_Release(&ord); PyBuffer_Release(&rn); PyBuffer_Release(&pool);
+      return NULL;
+    }
+    have_ref = 1;
+  }
 #define OPT(name) PyDict_GetItemString(opts, name)
   PyObject *o_prefix = OPT("id_prefix"), *o_fmt = OPT("genotype_format"), *o_none = OPT("genotype_none");
   if (!o_prefix || !o_fmt || !o_none || !OPT("mosaic") || !OPT("mosaic_af_max") || !OPT("output_rnames") || !OPT("nm") || !OPT("phase") ||
@@ -1688,6 +1706,15 @@ static PyObject* py_vcf_records(PyObject* self, PyObject* args) {
   const long long n_rec = rec.len / (long long)sizeof(snf_call_t), n_ord = ord.len / 8, rn_n = rn.len / 4;
   const int64_t* O = (const int64_t*)ord.buf;
   const uint32_t* RN = (const uint32_t*)rn.buf;
+  const int64_t *DI = NULL, *DOFF = NULL, *OOFF = NULL; const int32_t *DST = NULL, *DN = NULL, *OST = NULL;
+  long long n_dq = 0;
+  if (have_ref) {
+    DI = (const int64_t*)q_didx.buf; DOFF = (const int64_t*)q_doff.buf; OOFF = (const int64_t*)q_ooff.buf;
+    DST = (const int32_t*)q_dst.buf; DN = (const int32_t*)q_dn.buf; OST = (const int32_t*)q_ost.buf;
+    n_dq = q_dst.len / 4;
+    if (q_didx.len / 8 != n_ord || q_ooff.len / 8 != n_ord + 1 || q_ost.len / 4 != n_ord || q_doff.len / 8 != n_dq + 1 || q_dn.len / 4 != n_dq) {
+      PyErr_SetString(PyExc_ValueError, "vcf_records: the reference query tables do not fit the records"); goto done; }
+  }
   for (long long k = 0; k < n_ord; k++) {
     if (O[k] < 0 || O[k] >= n_rec) { PyErr_SetString(PyExc_ValueError, "record index outside the table"); goto done; }
     const snf_call_t* c = &C[O[k]];
@@ -1704,18 +1731,48 @@ static PyObject* py_vcf_records(PyObject* self, PyObject* args) {
     if (ins && svlen < minsvlen) continue;
     const long long end = (c->precise && c->svtype == SNF_DEL) ? pos + (svlen < 0 ? -svlen : svlen) : c->end;
     const size_t line_start = b.n;
+    /* REF / ALT against the fetched reference bases: VCF._resolve_sequences (vcf.py:302-342), statement for statement */
+    const char *refp = "N", *del_alt = NULL; size_t reflen = 1;
+    int got_base = 0;                        /* the one-base fetch succeeded */
+    int one_base = 0;                        /* the `call.ref == "N"` branch runs: the one-base fetch, then the IUPAC table over REF and ALT */
+    const char* basep = "N"; size_t baselen = 1;      /* what stands where the ALT of an INS / BND holds the reference base */
+    if (have_ref && !symbolic) {
+      if (c->svtype == SNF_DEL && DI[k] >= 0) {
+        const int64_t d = DI[k];
+        if (d >= n_dq || DOFF[d] < 0 || DOFF[d + 1] < DOFF[d] || DOFF[d + 1] > q_dpool.len) { PyErr_SetString(PyExc_ValueError, "deletion query outside its tables"); goto done; }
+        if (DST[d] == 0) {
+          reflen = (size_t)(DOFF[d + 1] - DOFF[d]); refp = (const char*)q_dpool.buf + DOFF[d];
+          if (reflen == 0) { PyErr_SetString(PyExc_IndexError, "string index out of range"); goto done; }      /* call.ref[0] of an empty fetch */
+          del_alt = refp;
+          if (DN[d] > 0 && (double)DN[d] / (double)reflen > max_unknown) continue;      /* not written, not counted */
+        }
+      }
+      one_base = reflen == 1 && refp[0] == 'N';
+      if (one_base && OST[k] == 0) {
+        if (OOFF[k] < 0 || OOFF[k + 1] < OOFF[k] || OOFF[k + 1] > q_opool.len) { PyErr_SetString(PyExc_ValueError, "base query outside its tables"); goto done; }
+        reflen = (size_t)(OOFF[k + 1] - OOFF[k]); refp = (const char*)q_opool.buf + OOFF[k];
+        basep = refp; baselen = reflen; got_base = 1;
+      }
+    }
     /* CHROM POS ID REF ALT */
     if (ob_py(&b, contig) || OB_LIT(&b, "\t") || ob_ll(&b, pos) || OB_LIT(&b, "\t") || ob_py(&b, o_prefix)) goto done;
     { char idbuf[64]; snprintf(idbuf, sizeof idbuf, "%s.%XS%llX", SVTYPES[c->svtype], (unsigned)c->sv_id, (unsigned long long)task_id);
-      if (ob_str(&b, idbuf) || OB_LIT(&b, "\tN\t")) goto done; }
+      if (ob_str(&b, idbuf) || OB_LIT(&b, "\t")) goto done; }
+    const size_t ref_at = b.n;
+    if (ob_put(&b, refp, reflen) || OB_LIT(&b, "\t")) goto done;
     if (bnd) {     /* sv.py:630-634; also with --symbolic (vcf.py:322-324 leaves BND ALTs alone) */
       const char* br = c->bnd_is_reverse ? "]" : "[";
-      if (ob_str(&b, c->bnd_is_first ? "N" : "") || ob_str(&b, br) || ob_name(&b, contig_names, c->mate_contig, "ctg") || OB_LIT(&b, ":") ||
-          ob_ll(&b, c->mate_ref_start) || ob_str(&b, br) || ob_str(&b, c->bnd_is_first ? "" : "N")) goto done;
+      if ((c->bnd_is_first && ob_put(&b, basep, baselen)) || ob_str(&b, br) || ob_name(&b, contig_names, c->mate_contig, "ctg") || OB_LIT(&b, ":") ||
+          ob_ll(&b, c->mate_ref_start) || ob_str(&b, br) || (!c->bnd_is_first && ob_put(&b, basep, baselen))) goto done;
     } else if (resolved) {
-      if (ob_put(&b, (const char*)pool.buf + c->alt_off, (size_t)c->alt_len)) goto done;
+      if ((got_base && ob_put(&b, basep, baselen)) || ob_put(&b, (const char*)pool.buf + c->alt_off, (size_t)c->alt_len)) goto done;      /* a failed fetch prepends nothing */
+    } else if (del_alt) {
+      if (ob_put(&b, del_alt, 1)) goto done;
     } else {
       if (OB_LIT(&b, "<") || ob_str(&b, SVTYPES[c->svtype]) || OB_LIT(&b, ">")) goto done;
+    }
+    if (one_base) {      /* str.translate(_IUPAC_TO_N) over REF and the whole ALT: symbolic ALTs and mate names too */
+      for (size_t q = ref_at; q < b.n; q++) if (strchr("RYSWKMBDHV", b.p[q]) && b.p[q]) b.p[q] = 'N';
     }
     /* QUAL FILTER */
     { const long long q = c->qual < 0 ? 0 : c->qual > 60 ? 60 : c->qual;
@@ -1770,6 +1827,10 @@ static PyObject* py_vcf_records(PyObject* self, PyObject* args) {
 done:
   free(b.p);
   PyBuffer_Release(&rec); PyBuffer_Release(&ord); PyBuffer_Release(&rn); PyBuffer_Release(&pool);
+  if (have_ref) {
+    PyBuffer_Release(&q_didx); PyBuffer_Release(&q_dpool); PyBuffer_Release(&q_doff); PyBuffer_Release(&q_dst); PyBuffer_Release(&q_dn);
+    PyBuffer_Release(&q_opool); PyBuffer_Release(&q_ooff); PyBuffer_Release(&q_ost);
+  }
   return ret;
 }
 

@@ -111,6 +111,21 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.snf_deflate_last_error.restype = C.c_char_p
     for f in ("snf_deflate_create", "snf_deflate_run"):
         getattr(lib, f).restype = C.c_int
+    i64 = C.c_int64
+    lib.snf_fasta_create.argtypes = [C.c_int, i64, C.POINTER(vp)]
+    lib.snf_fasta_load_text.argtypes = [vp, C.c_void_p, i64]
+    lib.snf_fasta_load_bgzf.argtypes = [vp, C.c_void_p, i64, C.c_void_p, i64, C.POINTER(C.c_float)]
+    lib.snf_fasta_index.argtypes = [vp, C.POINTER(abi.snf_fasta_index_result_t)]
+    lib.snf_fasta_set_index.argtypes = [vp, i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.snf_fasta_nruns.argtypes = [vp, i64, C.c_int32, C.c_int32, C.POINTER(abi.snf_fasta_runs_t)]
+    lib.snf_fasta_fetch.argtypes = [vp, i64, i64, C.c_void_p, C.c_void_p, C.POINTER(abi.snf_fasta_fetch_t)]
+    lib.snf_fasta_read_text.argtypes = [vp, i64, i64, C.c_void_p]
+    lib.snf_fasta_destroy.argtypes = [vp]
+    lib.snf_fasta_destroy.restype = None
+    lib.snf_fasta_last_error.restype = C.c_char_p
+    for f in ("snf_fasta_create", "snf_fasta_load_text", "snf_fasta_load_bgzf", "snf_fasta_index", "snf_fasta_set_index", "snf_fasta_nruns",
+              "snf_fasta_fetch", "snf_fasta_read_text"):
+        getattr(lib, f).restype = C.c_int
     lib.snf_batch_pass.argtypes = [vp]
     lib.snf_batch_open.argtypes = [C.POINTER(abi.snf_config_t), C.c_int, C.POINTER(abi.snf_task_input_t), C.c_int32, C.c_int, C.POINTER(vp)]
     for f in ("snf_batch_open", "snf_batch_pass", "snf_batch_create", "snf_batch_add_task", "snf_batch_upload", "snf_batch_call_candidates",

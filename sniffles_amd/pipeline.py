@@ -100,7 +100,10 @@ def mask_N_coverage(ti, fasta_handle, contig: str, regions) -> None:
     import logging
     from . import soa
     try:
-        ti.nmask_start, ti.nmask_end = soa.paint_nmask(fasta_handle.fetch, contig, regions, int(ti.contig_len))
+        if hasattr(fasta_handle, "nmask"):          # a device-resident reference (fasta.DeviceFasta): the runs of 'N' come from fa_nruns
+            ti.nmask_start, ti.nmask_end = fasta_handle.nmask(contig, regions, int(ti.contig_len))
+        else:
+            ti.nmask_start, ti.nmask_end = soa.paint_nmask(fasta_handle.fetch, contig, regions, int(ti.contig_len))
     except Exception as e:  # noqa: BLE001
         ti.nmask_start = ti.nmask_end = None
         logging.warning(f"Unable to mask N regions in coverage vector, reference could not be fetched: {e}")
@@ -163,7 +166,8 @@ def call_sample(records: bam.BamRecords, config, vcf_handle=None, snf_path=None,
     Writes the VCF to `vcf_handle` and / or the SNF to `snf_path` (CallTask.execute switches QC filtering off for the
     candidates when an SNF is requested, parallel.py:258-263).
     `objects=False`: VCF only, formatted straight from the record table (vcf.VCF.write_records) - the same text, no `SVCall`
-    objects (`SampleResult.calls` stays empty); falls back to the object path when a reference FASTA is attached.
+    objects (`SampleResult.calls` stays empty); with a reference FASTA attached this path serves a device-resident one
+    (`reference=fasta.open_device(path)`: REF / ALT from two batched fetches per task) and falls back to the object path for any other handle.
     `reference` / `config.reference`: the reference FASTA (see `open_reference`) - with it the coverage of every task is masked
     where the reference base is 'N' (`_mask_N_coverage`, leadprov.py:420-443, 470) and the writer resolves REF / ALT.
     `snf_deflater`: a `bgzfout.DeflateDevice` - the SNF blocks are compressed on the GPU (default: `gzip.compress` on this thread).

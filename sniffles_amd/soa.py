@@ -86,25 +86,33 @@ def paint_nmask(fetch, contig: str, regions, contig_len: int):
             continue
         if len(seq) == 1 and width != 1:
             seq = seq * width
-        cut = []                        # the slice is overwritten: what was painted inside it goes first
-        for s, e in cur:
-            if e <= lo or s >= hi:
-                cut.append((s, e))
-            else:
-                if s < lo:
-                    cut.append((s, lo))
-                if e > hi:
-                    cut.append((hi, e))
         ns, ne = nmask_intervals(seq)
-        cut.extend((int(a) + lo, int(b) + lo) for a, b in zip(ns.tolist(), ne.tolist()))
-        cut.sort()
-        cur = []
-        for s, e in cut:                # neighbours that touch become one interval (the library wants them disjoint and sorted)
-            if cur and s <= cur[-1][1]:
-                cur[-1] = (cur[-1][0], max(cur[-1][1], e))
-            else:
-                cur.append((s, e))
+        cur = paint_region(cur, lo, hi, ns.astype(np.int64) + lo, ne.astype(np.int64) + lo)
     return np.array([s for s, _ in cur], np.int32), np.array([e for _, e in cur], np.int32)
+
+
+def paint_region(cur: list, lo: int, hi: int, ns, ne) -> list:
+    """One `mask[lo:hi] = sequence` of `paint_nmask`: `cur`, the sorted disjoint [s, e) painted 'N' so far, with the slice [lo, hi)
+    overwritten by the runs (ns[], ne[]) of 'N' of the new sequence, in contig coordinates.  Host code on purpose: the order of the
+    regions is the reference's semantics (`paint_nmask` and `fasta.DeviceFasta.nmask` share it)."""
+    cut = []                            # the slice is overwritten: what was painted inside it goes first
+    for s, e in cur:
+        if e <= lo or s >= hi:
+            cut.append((s, e))
+        else:
+            if s < lo:
+                cut.append((s, lo))
+            if e > hi:
+                cut.append((hi, e))
+    cut.extend((int(a), int(b)) for a, b in zip(np.asarray(ns).tolist(), np.asarray(ne).tolist()))
+    cut.sort()
+    out = []
+    for s, e in cut:                    # neighbours that touch become one interval (the library wants them disjoint and sorted)
+        if out and s <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], e))
+        else:
+            out.append((s, e))
+    return out
 
 
 @dataclass

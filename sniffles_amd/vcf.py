@@ -335,9 +335,15 @@ class VCF:
 
     def can_write_records(self) -> bool:
         """The record-table writer serves the plain single-sample case: no reference FASTA attached (REF / ALT stay "N" /
-        the consensus), one sample column, no SVLENGTHS."""
+        the consensus) or one that is resident on the device (`fasta.DeviceFasta`: its bases come as batched fetches; any other handle
+        keeps the object path, one `fetch` per call), one sample column, no SVLENGTHS."""
         cfg = self.config
-        return (self.reference_handle is None and len(cfg.sample_ids_vcf) == 1 and cfg.sample_ids_vcf[0][0] == 0
+        ref = self.reference_handle
+        if ref is not None:
+            from .fasta import DeviceFasta
+            if not isinstance(ref, DeviceFasta):
+                return False
+        return (len(cfg.sample_ids_vcf) == 1 and cfg.sample_ids_vcf[0][0] == 0
                 and not cfg.dev_emit_sv_lengths and cfg.mode != "combine" and _fast() is not None)
 
     def write_records(self, res, ti, order) -> int:
@@ -350,9 +356,25 @@ class VCF:
                     output_rnames=bool(cfg.output_rnames), nm="NM" in self.info_order, phase=bool(cfg.phase), symbolic=bool(cfg.symbolic),
                     minsvlen=int(cfg.minsvlen), genotype_format=self.genotype_format,
                     genotype_none=format_genotype(self.default_genotype, cfg.phase))
-        text, n = _fast().vcf_records(np.ascontiguousarray(res.calls), np.ascontiguousarray(order, np.int64),
+        order = np.ascontiguousarray(order, np.int64)
+        extra = ()
+        ref = self.reference_handle
+        if ref is not None and not cfg.symbolic and len(order):      # (--symbolic fetches nothing, vcf.py:318-324)
+            # what `_resolve_sequences` fetches per call, as two batches on the device-resident reference: the deleted bases of every
+            # deletion up to max_del_seq_len, and the base at max(0, pos - 1) of every record
+            from .soa import SVTYPES
+            calls = res.calls[order]
+            pos, svlen = calls["pos"].astype(np.int64), calls["svlen"].astype(np.int64)
+            is_del = (calls["svtype"] == SVTYPES.index("DEL")) & (np.abs(svlen) <= int(cfg.max_del_seq_len))
+            del_idx = np.full(len(order), -1, np.int64)
+            del_idx[is_del] = np.arange(int(is_del.sum()))
+            dpool, doff, dst, dn = ref.fetch_many(ti.contig, (pos - 1)[is_del], (pos - svlen)[is_del])
+            start = np.maximum(0, pos - 1)
+            bpool, boff, bst, _ = ref.fetch_many(ti.contig, start, start + 1)
+            extra = ((del_idx, dpool, doff, dst, dn, bpool, boff, bst, float(cfg.max_unknown_pct)),)
+        text, n = _fast().vcf_records(np.ascontiguousarray(res.calls), order,
                                       np.ascontiguousarray(res.rnames, np.uint32), np.ascontiguousarray(res.alt_pool, np.uint8),
-                                      ti.qnames, ti.ps_names, ti.contig, int(ti.task_id), ti.contig_names, list(_filters()), opts)
+                                      ti.qnames, ti.ps_names, ti.contig, int(ti.task_id), ti.contig_names, list(_filters()), opts, *extra)
         self.handle.write(text.decode("utf-8"))
         self.call_count += n
         return n
