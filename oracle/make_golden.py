@@ -499,12 +499,30 @@ def main_genotype_vcf():
         fh.write(json.dumps(doc, sort_keys=True, separators=(",", ":")).encode())
 
 
+def main_genotype_edges():
+    """The genotype table at its edges: the reference's own postprocessing.genotype_sv over the directed record families of
+    tests/genotype_ref.py (stand-in calls of the reference's SVCall class); inputs and results only."""
+    import genotype_ref as gr
+    import ref_harness as rh
+    from sniffles_amd import sv
+    ref = rh.load_reference()
+    doc = {}
+    for name, over, records in gr.fixture_families():
+        exp = gr.on_objects(records, over, ref.sv.SVCall, sv.new_call, ref.postprocessing.genotype_sv, lambda: rh.make_config(()))
+        doc[name] = dict(config=over, records=records, expected=exp)
+        print(f"{name:24s} {len(records)} records, {sum(e['gt'] is not None for e in exp)} genotyped, "
+              f"{sum(e['filter'] == 'GT' for e in exp)} filtered by z-score")
+    with gzip.GzipFile(os.path.join(ROOT, "tests", "golden", "genotype_edges.json.gz"), "wb", mtime=0) as fh:
+        fh.write(json.dumps(doc, sort_keys=True, separators=(",", ":")).encode())
+
+
 if __name__ == "__main__":
     # python oracle/make_golden.py                 -> every fixture family
     # python oracle/make_golden.py vcf sample      -> only these families
     # python oracle/make_golden.py main fuzz_4_2   -> single cases of the `main` / `combine` families
     FAMILIES = dict(main=main, clusters=main_clusters, regenotype=main_regenotype, combine=main_combine, consensus=main_consensus, consensus_long=main_consensus_long, consensus_class_edges=main_consensus_class_edges, combine_task=main_combine_task,
-                    bam=main_bam_fixtures, extract=main_extract, snf=main_snf, vcf=main_vcf, sample=main_sample, genotype=main_genotype, population=main_population, genotype_vcf=main_genotype_vcf)
+                    bam=main_bam_fixtures, extract=main_extract, snf=main_snf, vcf=main_vcf, sample=main_sample, genotype=main_genotype, population=main_population, genotype_vcf=main_genotype_vcf,
+                    genotype_edges=main_genotype_edges)
     argv = sys.argv[1:]
     fams = [a for a in argv if a in FAMILIES] or list(FAMILIES)
     names = set(a for a in argv if a not in FAMILIES)

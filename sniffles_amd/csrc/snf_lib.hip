@@ -295,6 +295,7 @@ struct snf_batch_impl {
   int graph_mode = 0;             // set at upload: 2 = replay (small batches, or SNF_GRAPH=1), 0 = eager, 1 = replay only while no other batch of
                                   // this process has a pass in flight
   bool in_flight = false;         // counted in its device's DevicePacing::passes_in_flight
+  bool side_open = false;         // a candidate stage has left work on the side / fourth stream that the main stream has not waited for yet
   int slot_fd = -1;               // the GPU slot this pass holds (SNF_GPU_SLOTS)
   double pass_start_ms = 0.0;     // when this handle's pass in flight began (pacing of overlapping passes)
   bool capturing = false;         // run_pass is capturing this pass into a graph
@@ -733,6 +734,7 @@ void stage_reads(const snf_task_input_t& t, uint8_t* st, const size_t* off, int6
 
 void enqueue_read_index(snf_batch_impl* b);
 void enqueue_pass_init(snf_batch_impl* b);
+void join_open_candidates(snf_batch_impl* b);
 void enqueue_keys(snf_batch_impl* b);
 // coverage samples by the thread-per-call kernel d4_coverage instead of d4s_coverage (launch_coverage)
 bool coverage_per_call(const snf_batch_impl* b) { return b->k.d4_thread || !b->v.wave_path; }
@@ -1414,6 +1416,7 @@ void run_call_candidates(snf_batch_impl* b) {
   b->reads_ready = true; b->cov_avg_ready = true; b->finalized = false;
   begin_pass_timing(b);
   pass_begins(b);
+  join_open_candidates(b);
   b->chain_slot = -1;
   if (process_knobs().chain_gate && !b->capturing) {
     DevicePacing& P = pacing_of(b);
@@ -1607,12 +1610,23 @@ void run_call_candidates(snf_batch_impl* b) {
   }
   b->res_current = false;
   v.out_valid = 0;
+  b->side_open = true;
 }
 
 // everything enqueued on any of the batch's streams has completed and the pinned result block is current
 void join_fourth(snf_batch_impl* b) {  // main stream waits for the fourth stream (sv ids, read names, their copy)
   SNF_HIP(hipEventRecord(b->ev_join4, b->stream4));
   SNF_HIP(hipStreamWaitEvent(b->stream, b->ev_join4, 0));
+  b->side_open = false;   // (every caller joins the side stream right before)
+}
+// A candidate stage ends with work on the side stream (coverage samples) and on the fourth (sv ids, read names) that only finalize or a
+// fetch makes the main stream wait for.  A candidate stage enqueued straight behind another one must wait for it as well: its first
+// kernel resets the counters, flags and tile sums those two streams are still reading and publishing.  Nothing to do - and no event -
+// in the usual order call_candidates, finalize.
+void join_open_candidates(snf_batch_impl* b) {
+  if (!b->side_open || b->capturing) return;
+  join_side(b);
+  join_fourth(b);
 }
 void full_sync(snf_batch_impl* b) {
   join_side(b);
@@ -1941,6 +1955,7 @@ bool pass_graph_ok(snf_batch_impl* b) {
 void run_pass(snf_batch_impl* b) {
   View& v = b->v;
   pass_begins(b);
+  join_open_candidates(b);      // (before a replay or a capture: the wait is on events recorded outside either)
   if (!pass_graph_ok(b)) { run_call_candidates(b); run_finalize(b); return; }
   // (the pinned blocks of the result are chosen by run_finalize from b->hb_out / hb_alt: stable once they have been sized by a first pass)
   const auto key = std::make_tuple((void*)b->hb_out.p, (void*)b->hb_alt.p, v.out_mode);

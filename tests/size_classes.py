@@ -3,7 +3,8 @@ tests/test_knobs.py reads the switches), and the ladders t - 1, t, t + 1 the dir
 tests/test_size_classes.py are derived from.  A threshold that is no longer found is an error, not a default: a case that
 silently tests the middle of a class is what this module is there to prevent.  ed_thresholds(): the same for the edit-distance
 kernels and the merge kernel that calls them (tests/ed_edges.py, tests/test_edit_distance_edges.py).  extract_thresholds(): the same
-for the extraction kernels (tests/extract_edges.py, tests/test_extract_edges.py)."""
+for the extraction kernels (tests/extract_edges.py, tests/test_extract_edges.py).  coverage_thresholds(): the same for the read-table rank
+index, the coverage kernels on it and the genotype table (tests/coverage_cases.py, tests/test_coverage_edges.py, tests/test_genotype_edges.py)."""
 import os
 import re
 
@@ -126,6 +127,30 @@ def extract_thresholds():
         grid_cap=1 << int(_one(r'int grid_cap = env_set\("SNF_EXTRACT_GRID"\) \? env_pos\("SNF_EXTRACT_GRID", 1\) : \(1 << (\d+)\);', knobs,
                                "the default grid cap of the wave form")),
         waves=int(_one(r'int waves = env_int\("SNF_EXTRACT_WAVES", (\d+)\);', knobs, "the default of SNF_EXTRACT_WAVES")),
+    )
+
+
+def coverage_thresholds():
+    """dict of the sizes of the read-table rank index (snf_exact.h: every 2^SNF_TOP_SHIFT-th global position is sampled), of the chunks of
+    the coverage sums (snf_wave_call.h: reads per workgroup round of d5w_covsum, the kernel every pass launches - the literal of the
+    kernel and the two of its grid in snf_lib.hip have to agree; snf_stage_call.h: positions per thread of d5x_covexact, and
+    SNF_COV_CHUNK of d5_covsum, a thread form that is instantiated and launched by nothing), of the depth from which a task takes the
+    exact walk (the uint16 wrap decision of the upload, snf_lib.hip) and of the side of the genotype table (snf_view.h)."""
+    lib_hip = _src("snf_lib.hip")
+    ch = _one(r"__global__ void __launch_bounds__\(256\) d5w_covsum\(const View v, int64_t n_unused\) \{\n[^\n]*\n[^\n]*\n\s*const int64_t CH = (\d+);",
+              _src("snf_wave_call.h"), "the chunk of d5w_covsum")
+    grid = _one(r"int64_t grid = \(R \+ (\d+)\) / (\d+); if \(grid > \d+\) grid = \d+;\n\s*hipLaunchKernelGGL\(d5w_covsum,", lib_hip, "the grid of d5w_covsum")
+    if not (int(ch) == int(grid[0]) + 1 == int(grid[1])):
+        raise AssertionError(f"size_classes: the chunk of d5w_covsum is written as different numbers {(ch,) + tuple(grid)}")
+    if len(re.findall(r"\bd5_covsum\b", lib_hip)) != 1:
+        raise AssertionError("size_classes: d5_covsum is no longer named exactly once (its instantiation) in snf_lib.hip - if it is launched, it needs cases")
+    return dict(
+        covsum_chunk=int(ch),
+        top_shift=_define("SNF_TOP_SHIFT", "snf_exact.h"),
+        cov_chunk=_define("SNF_COV_CHUNK", "snf_stage_call.h"),
+        covx_chunk=_define("SNF_COVX_CHUNK", "snf_stage_call.h"),
+        gt_n=_define("SNF_GT_N", "snf_view.h"),
+        wrap_depth=int(_one(r"if \(masked \|\| maxd\[\(size_t\)t\] >= (\d+) \|\| b->k\.cov_exact\)", lib_hip, "the uint16 wrap decision of the upload")),
     )
 
 

@@ -11,6 +11,7 @@ import pytest
 
 import cases
 import golden_util as gu
+from coverage_ref import dense_block_coverage      # (the reference's formula on the dense vector)
 import snf_util as su
 from sniffles_amd import leadprov, parallel, snf, sv
 from sniffles_amd.config import SnifflesConfig
@@ -172,17 +173,6 @@ def test_reference_reads_our_files(tmp_path):
         assert objs and all(type(c) is ref.sv.SVCall for c in objs)
         assert norm(su.file_record(f, ti.contig, ref.sv.TYPES)) == doc["files"][s]["record"]
         f.close()
-
-
-def dense_block_coverage(ti, binsize):
-    cov = np.zeros(ti.contig_len, np.uint16)
-    for s, e in zip(ti.read_start.tolist(), ti.read_end.tolist()):
-        cov[s:e] += 1                                   # (uint16: wraps at 65536 like the reference's vector, leadprov.py:451, 510)
-    if getattr(ti, "nmask_start", None) is not None:    # _mask_N_coverage (leadprov.py:420-443)
-        for a, e in zip(ti.nmask_start.tolist(), ti.nmask_end.tolist()):
-            cov[a:e] = 0
-    pad = -len(cov) % binsize
-    return [round(x) for x in np.pad(cov, (0, pad), mode="constant").reshape(-1, binsize).mean(axis=1)]
 
 
 def check_block_coverage(tis, _lib, binsizes):
