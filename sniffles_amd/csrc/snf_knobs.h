@@ -41,6 +41,8 @@ struct BatchKnobs {
   int win_bits_max = env_int("SNF_WIN_BITS_MAX", 10); // SNF_WIN_BITS_MAX=k, default 10: widest window tried (measured on the 30x genome: 10 beats 9 and 8)
   bool w4_split = env_on("SNF_W4_SPLIT");            // SNF_W4_SPLIT!=0: w4s_segment as its small instance + the large one over a list; default: one launch
   bool pool_slices = !env_set("SNF_NO_POOL_SLICES"); // SNF_NO_POOL_SLICES (set): fused sequences through the shared counter only; default: a private slice per resident wave
+  int fuse_copy = env_set("SNF_FUSE_COPY") ? env_on("SNF_FUSE_COPY") : -1;   // SNF_FUSE_COPY=0/1: the parts of fused sequences copied inside the refine kernels / by d1c_fusecopy
+                                                     //   on the side stream; unset (-1): the side stream for handles whose passes are eager, in place for those that replay a graph
   bool merge_reread = env_on("SNF_MERGE_REREAD");    // SNF_MERGE_REREAD!=0: merged cluster metrics read again instead of added (tests/test_clusters.py)
   int run_gap = env_int("SNF_RUN_GAP", KNOB_UNSET);  // SNF_RUN_GAP=<bp>: cut width of the parallel merge scan (negative: whole group serial);
                                                      //   unset: max(1000, cluster_merge_bnd, cluster_repeat_h_max) - resolved at create

@@ -326,6 +326,8 @@ struct snf_batch_impl {
   Counts* h_cnt = nullptr;        // counters as last read back (lives in the pinned result block hb_res)
   void* sort_tmp[2] = {nullptr, nullptr}; size_t sort_tmp_bytes[2] = {0, 0};  // rocPRIM temp storage per stream
   hipEvent_t ev_cls_fork = nullptr, ev_cls_join = nullptr;   // grouped kernel of a refine / call stage beside its partner (ClassFork)
+  hipEvent_t ev_refined = nullptr, ev_fcopy = nullptr;       // refine stage enqueued (main; where ClassFork has not recorded one anyway) -> d1c_fusecopy (side) -> first reader of pool bytes (main)
+  bool fcopy_open = false;        // d1c_fusecopy of the current candidates is enqueued and the main stream has not waited for it yet
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork3 = nullptr, ev_join3 = nullptr, ev_base = nullptr,
              ev_counts = nullptr, ev_rn = nullptr, ev_join4 = nullptr, ev_e3 = nullptr;  // host waits: counters published (main), read-name total published (side)
   // growable finalize scratch
@@ -469,6 +471,13 @@ void join_classes(snf_batch_impl* b) {
 }
 void join_side(snf_batch_impl* b) {  // main stream waits for everything enqueued on the side stream so far
   SNF_HIP(hipStreamWaitEvent(b->stream, b->ev_join, 0));
+}
+// The parts of fused sequences are copied on the side stream (enqueue_fuse_copy).  In front of the first kernel of the main stream - or of
+// a stream forked from it - that reads pool bytes: the ALT stage.  Everything before it reads F_seq_off / F_seq_len only.
+void join_fuse_copy(snf_batch_impl* b) {
+  if (!b->fcopy_open) return;
+  SNF_HIP(hipStreamWaitEvent(b->stream, b->ev_fcopy, 0));
+  b->fcopy_open = false;
 }
 template <class T>
 T* upload_vec(snf_batch_impl* b, const std::vector<T>& h, size_t extra = 0) {
@@ -1024,6 +1033,7 @@ void do_upload(snf_batch_impl* b) {
   v.grp_dirty = dalloc<int32_t>(b, 8 * (size_t)T + 8); v.grp_seed_lo = dalloc<int32_t>(b, 8 * (size_t)T + 8);
   v.grp_seed_hi = dalloc<int32_t>(b, 8 * (size_t)T + 8);
   v.F_seq_off = dalloc<int64_t>(b, N1);
+  v.fcopy = dalloc<FuseDesc>(b, N1); dzero(b, v.fcopy, N1 * sizeof(FuseDesc));      // (a recycled slab may hold another batch's entries)
   v.cand = dalloc<snf_call_t>(b, N1); v.candx = dalloc<CallX>(b, N1);
   v.calls = dalloc<snf_call_t>(b, N1); v.callx = dalloc<CallX>(b, N1);
   v.rnames = dalloc<uint32_t>(b, 2 * (size_t)N + 1);
@@ -1044,6 +1054,10 @@ void do_upload(snf_batch_impl* b) {
   const bool small_batch = N <= 400000;
   v.chain_on = b->k.chain >= 0 ? b->k.chain : (small_batch ? 1 : 0);
   b->graph_mode = (b->k.graph >= 0 ? b->k.graph != 0 : small_batch) ? 2 : 0;
+  // Fused sequences copied on the side stream (enqueue_fuse_copy): as with the classes side by side (ClassFork), only handles whose passes
+  // are eager take the edge by default - replayed from a graph the kernel and its two edges cost a launch-bound batch more than the
+  // shorter refine kernels give (chr20 alone: 0.35 against 0.27 ms per step).  SNF_FUSE_COPY = 0 / 1 forces either.
+  v.fuse_defer = v.wave_path && (b->k.fuse_copy >= 0 ? b->k.fuse_copy != 0 : b->graph_mode == 0) ? 1 : 0;
   v.big_cap = (int64_t)(N1 / 64 + 2); v.big_cnt = dalloc<uint32_t>(b, 3 * 64 * 16); v.big_list = dalloc<int32_t>(b, (size_t)(3 * 64 * v.big_cap));
   v.big_wave = v.wave_path;
   { const int hn = b->k.heavy_n; v.heavy_n = hn > 8 && hn < 64 ? hn : 0; }      // (0 / out of range: one class, as before)
@@ -1157,9 +1171,9 @@ void do_upload(snf_batch_impl* b) {
   b->reads_ready = true;
   b->uploaded = true;
   if (v.prof) fprintf(stderr, "[SNF_PROF] read index (sorted ends, hap prefix counts): %.2f ms\n", now_ms() - t_index0);
-  if (v.prof) fprintf(stderr, "[SNF_PROF] forms: %s path, %s scans, coverage by %s, grouped refine %s, grouped call %s\n", v.wave_path ? "wave" : "thread",
+  if (v.prof) fprintf(stderr, "[SNF_PROF] forms: %s path, %s scans, coverage by %s, grouped refine %s, grouped call %s, fused copies %s\n", v.wave_path ? "wave" : "thread",
                       b->fused ? "fused" : "rocPRIM", coverage_per_call(b) ? "d4_coverage" : "d4s_coverage", v.wave_path && b->k.d1_groups ? "on" : "off",
-                      v.wave_path && b->k.d2_groups ? "on" : "off");
+                      v.wave_path && b->k.d2_groups ? "on" : "off", v.fuse_defer ? "on the side stream" : "in place");
   if (v.prof) fprintf(stderr, "[SNF_PROF] upload: %.1f ms (stage %.1f, H2D %.1f [%.1f MB], allocations + derived %.1f = packing + arrays %.2f, prefilter count %.2f, "
                               "window width %.2f, read index %.2f; %zu device allocations)\n",
                       now_ms() - t_begin, t_staged - t_begin, t_copied - t_staged, (double)at / 1e6, now_ms() - t_copied, t_alloc - t_copied, t_pfcount - t_alloc,
@@ -1407,6 +1421,26 @@ void enqueue_window_front(snf_batch_impl* b) {
   LAUNCH_Q(w6t_emit, v, N, 0);
 }
 
+// The byte copies of merge_inner's fused sequences, off the chain: the refine kernels have recorded source, length and destination
+// of every part (View::fcopy); d1c_fusecopy moves the bytes on the side stream - idle between the read preparation and the coverage
+// samples - while the main stream goes on with the refined-cluster table and the call stage, which read no pool bytes.  (Not the
+// fourth stream: d2g_call runs there.)  It starts behind `after`, an event of the main stream behind both refine kernels that the caller
+// has recorded anyway (the fork of the call stage's classes), or else behind one recorded here: an event record costs the main stream
+// ~8 us in front of its next kernel.  join_fuse_copy is the other end of the edge.
+void enqueue_fuse_copy(snf_batch_impl* b, hipEvent_t after) {
+  View& v = b->v;
+  if (!after) { SNF_HIP(hipEventRecord(b->ev_refined, b->stream)); after = b->ev_refined; }
+  SNF_HIP(hipStreamWaitEvent(b->stream2, after, 0));
+  hipStream_t prev = b->cur; b->cur = b->stream2;
+  { Scope _s(b, "d1c_fusecopy", 0);
+    int64_t grid = (v.NS + 63) / 64; if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(d1c_fusecopy, dim3((unsigned)grid), dim3(64), 0, b->cur, v, (int64_t)0);
+    SNF_HIP(hipGetLastError()); }
+  b->cur = prev;
+  SNF_HIP(hipEventRecord(b->ev_fcopy, b->stream2));
+  b->fcopy_open = true;
+}
+
 void run_call_candidates(snf_batch_impl* b) {
   SNF_TRACE("snf_batch_call_candidates (enqueue)");
   b->pass_idle = false;
@@ -1503,17 +1537,17 @@ void run_call_candidates(snf_batch_impl* b) {
       // grouped kernel goes beside the other one (ClassFork), in a captured pass they stay in line
       { ClassFork _f(b);
         Scope _s(b, "d1g_refine8", N * 36 / 3);
-        hipLaunchKernelGGL(d1g_refine<8>, dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
+        hipLaunchKernelGGL((v.fuse_defer ? d1g_refine<8, true> : d1g_refine<8, false>), dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
         SNF_HIP(hipGetLastError()); }
       { Scope _s(b, "d1w_refine", N * 36 - N * 36 / 3);
         v.d1_from_list = 1;
-        hipLaunchKernelGGL(d1w_refine, dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
+        hipLaunchKernelGGL((v.fuse_defer ? d1w_refine<true> : d1w_refine<false>), dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
         v.d1_from_list = 0;
         SNF_HIP(hipGetLastError()); }
       join_classes(b);      // (x_big<0> and the rc table need both)
     } else if (v.wave_path) {
       Scope _s(b, "d1w_refine", N * 36);
-      hipLaunchKernelGGL(d1w_refine, dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
+      hipLaunchKernelGGL((v.fuse_defer ? d1w_refine<true> : d1w_refine<false>), dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
       SNF_HIP(hipGetLastError());
     }
     if (!(v.wave_path && b->fused)) LAUNCH_Q(d1_refine, v, N, v.wave_path ? 0 : N * 36);   // (next to the wave kernels every item would return at once)
@@ -1533,6 +1567,9 @@ void run_call_candidates(snf_batch_impl* b) {
       prim_exscan<uint32_t>(b, v.rcflag, v.rcscan, N + 1, "scan_refined");
       LAUNCH_Q(d1b_rctable, v, N, N * 4);
     }
+    // (the fused sequences' copies go to the side stream here, behind the read preparation, which need not wait for the refine kernels)
+    const bool call_forks = v.wave_path && b->k.d2_groups && classes_beside(b);
+    if (v.fuse_defer && !call_forks) enqueue_fuse_copy(b, nullptr);
     if (v.wave_path && b->k.d2_groups) {
       // call_from by cluster size (snf_wave_call_g.h): eight clusters of <= 8 leads per wave; d2w_call - a wave per cluster - for the
       // others, from the list d1b_emit built (with the mid class: two of <= 32 per wave from list 0, d2w_call from list 1).  As in the
@@ -1545,6 +1582,7 @@ void run_call_candidates(snf_batch_impl* b) {
         if (ph) hipLaunchKernelGGL((d2g_call<8, 4, true>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         else hipLaunchKernelGGL((d2g_call<8, 4, false>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
         SNF_HIP(hipGetLastError()); }
+      if (v.fuse_defer && call_forks) enqueue_fuse_copy(b, b->ev_cls_fork);      // (the event ClassFork has just recorded behind d1bk_rctable)
       const bool mid = b->k.d2_mid;
       if (mid) { Scope _s(b, "d2g_call32", 0);
         if (ph) hipLaunchKernelGGL((d2g_call<32, 4, true>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
@@ -1700,6 +1738,7 @@ void enqueue_output_head(snf_batch_impl* b) {
 void run_alt_fallback(snf_batch_impl* b) {
   SNF_TRACE("E: slow ALT kernels (ROWS / thread form)");
   View& v = b->v;
+  join_fuse_copy(b);
   d2h(b, b->h_cnt, v.cnt, sizeof(Counts));
   dsync(b);
   const Counts& c = *b->h_cnt;
@@ -1902,6 +1941,7 @@ void run_finalize(snf_batch_impl* b) {
       b->hist_small = (int64_t)c.n_cls[1]; b->hist_large = (int64_t)(c.n_cls[2] + c.n_cls[3] + c.n_cls[4] + c.n_cls[5]); b->hist_copy = (int64_t)c.n_cls[0];
       b->hist_calls = c.n_calls; b->have_hist = true;
     }
+    join_fuse_copy(b);          // (the consensus kernels and e4c_copy read the fused bytes; e2a / e3b above only offsets and lengths)
     enqueue_consensus_wave(b, b->hist_small + 1, b->hist_large + 1, b->hist_copy + 1);
     stage_copy_alt(b);          // (staged result: the ALT section leaves behind the last ALT kernel)
     join_side(b);
@@ -1922,6 +1962,7 @@ void run_finalize(snf_batch_impl* b) {
     prim_exscan<int64_t>(b, v.sz_rd, v.sc_rd, nc + 1, "scan_cons_sizes");
     LAUNCH_Q(e3_conslist, v, nc + 1, 0);
     if (v.wave_path) {
+      join_fuse_copy(b);
       d2h(b, b->h_cnt, v.cnt, sizeof(Counts));
       dsync(b);
       const Counts& c = *b->h_cnt;
@@ -2690,7 +2731,7 @@ static DevInfo device_info(int device, int o2, int o1, WaveKernel k_d2w, WaveKer
     hipDeviceProp_t prop;
     SNF_HIP(hipGetDeviceProperties(&prop, device));
     DevInfo d{prop.multiProcessorCount, 0, 0, 0};
-    SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_d1w, d1w_refine, 64, 0));
+    SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_d1w, d1w_refine<false>, 64, 0));
     SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_d2w, k_d2w, 64, 0));
     SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_e1w, k_e1w, 64, 0));
     it = known.emplace(Key(device, o2, o1), d).first;
@@ -2720,6 +2761,8 @@ int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out) {
     SNF_HIP(hipEventCreateWithFlags(&b->ev_fork3, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_cls_fork, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_cls_join, hipEventDisableTiming));
+    SNF_HIP(hipEventCreateWithFlags(&b->ev_refined, hipEventDisableTiming));
+    SNF_HIP(hipEventCreateWithFlags(&b->ev_fcopy, hipEventDisableTiming));
     SNF_HIP(hipEventCreate(&b->ev_base));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_counts, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_rn, hipEventDisableTiming));
@@ -2809,6 +2852,8 @@ void snf_batch_destroy(snf_batch_t* bb) {
   if (b->ev_fork3) (void)hipEventDestroy(b->ev_fork3);
   if (b->ev_cls_fork) (void)hipEventDestroy(b->ev_cls_fork);
   if (b->ev_cls_join) (void)hipEventDestroy(b->ev_cls_join);
+  if (b->ev_refined) (void)hipEventDestroy(b->ev_refined);
+  if (b->ev_fcopy) (void)hipEventDestroy(b->ev_fcopy);
   if (b->ev_e3) (void)hipEventDestroy(b->ev_e3);
   if (b->ev_base) (void)hipEventDestroy(b->ev_base);
   if (b->ev_counts) (void)hipEventDestroy(b->ev_counts);

@@ -114,6 +114,19 @@ struct CallX {  // per-call internals that are not part of snf_call_t
 // lead, hi = end of its lead range.  s2 == ~0: not kept, a merge reads the leads.
 struct ClusterSums { int64_t sum, s1; uint64_t s2; int32_t x0, hi; };
 
+// One part of a fused sequence (merge_inner: curr_lead.seq += to_merge.seq) that the refine kernels leave to d1c_fusecopy
+// (snf_wave_refine.h): `len` pool bytes from `src` to `dst`.  Pool offsets fit 40 bits; the length sits in the upper 24 bits of the
+// two words (low 24 bits in a, the rest in b).  All zero: nothing to copy.
+struct alignas(16) FuseDesc {
+  uint64_t a, b;
+  SNF_HD static FuseDesc make(int64_t src, int32_t len, int64_t dst) {
+    return FuseDesc{(uint64_t)src | ((uint64_t)((uint32_t)len & 0xffffffu) << 40), (uint64_t)dst | ((uint64_t)((uint32_t)len >> 24) << 40)};
+  }
+  SNF_HD int64_t src() const { return (int64_t)(a & 0xffffffffffull); }
+  SNF_HD int64_t dst() const { return (int64_t)(b & 0xffffffffffull); }
+  SNF_HD int32_t len() const { return (int32_t)((a >> 40) | ((b >> 40) << 24)); }
+};
+
 struct View {
   snf_config_t cfg;
   int32_t T;          // tasks
@@ -250,6 +263,11 @@ struct View {
   // F: leads after merge_inner (fused), slot space = L index space; FI: final per-refined-cluster order -> F slot
   int32_t *F_orig, *F_svlen, *F_seq_len; int64_t* F_seq_off; uint8_t* F_sel; int32_t* FI;
   int32_t* F_lpos;           // L position (Lrec index) of the fused lead's head
+  // [N+1] slot space (a cluster's lo + sorted lane): the parts of fused sequences d1g_refine / d1w_refine left to d1c_fusecopy.  All zero
+  // at upload (a recycled slab may hold another batch's entries) and between passes: the copy kernel clears what it has acted on, so an
+  // entry is acted on once, in the pass that wrote it.  fuse_defer = 0 (handles that replay their passes from a graph, SNF_FUSE_COPY=0, and wherever the wave kernels do not run):
+  // the refine kernels copy in place and the table stays zero
+  FuseDesc* fcopy; int32_t fuse_defer, _pad_fd;
   int32_t *rc_n_s, *rc_cl_s; uint8_t* rc_keeplong_s;   // slot space (sparse): slot = F position of the rc's first lead
   int32_t *rc_lo, *rc_n, *rc_cluster; uint8_t* rc_keeplong;              // dense
   snf_call_t* cand; CallX* candx;                                         // per rc

@@ -71,9 +71,10 @@ SNF_D void big_push(const View& v, int kind, int32_t item) {
 // the input pool to its place in the fused lead's slice, all 64 lanes on one part at a time.  The parts are taken FOUR at a time: their
 // loads are requested together and stored together.  (One part after the other - load, store, next part - was a dependent round trip per
 // part: ~100 us per fusing cluster, a third of a wave's time in d1w_refine; source and destination never overlap - the slices lie behind
-// the input sequences.)  Measured and not kept (round 6, profiles/ab_r06_17.log): clusters with more than eight parts leaving their copies
-// to a copy kernel of their own behind d1w_refine (a wave per part) - the one workgroup d1w_refine ends with goes from 72 to 46-55 us,
-// the kernel from 72 to 63-67, and the copy kernel's launch costs the chain the 11 us back: 0.932-0.934 against 0.935-0.937 ms per step.
+// the input sequences.)  Who calls it: d1c_fusecopy below, on the side stream, for the parts the refine kernels have recorded (the
+// default), and the refine kernels themselves in their in-place instances (handles that replay a graph; SNF_FUSE_COPY=0).  Round 6 (profiles/ab_r06_17.log) had a
+// copy kernel BEHIND d1w_refine on the main stream, for clusters of more than eight parts only: its launch cost the chain what the
+// shorter refine kernel gave.
 SNF_D void wave_copy_parts(const View& v, int lane, bool p_act, int64_t p_src, int32_t p_len, int64_t p_dst) {
   typedef uint4 __attribute__((aligned(1))) u128_any;
   unsigned long long pm = __ballot(p_act && p_len > 0);
@@ -102,6 +103,34 @@ SNF_D void wave_copy_parts(const View& v, int lane, bool p_act, int64_t p_src, i
       for (int32_t bb = SNF_WAVE * 16 + lane * 16; bb < nfull; bb += SNF_WAVE * 16)      // (sequences beyond 1 KB: the rest, 1 KB per step)
         *(u128_any*)(v.pool + dt[k] + bb) = *(const u128_any*)(v.pool + so[k] + bb);
     }
+  }
+}
+
+// The parts of the fused leads a refine kernel holds in its lanes (sorted order; slot = the cluster's lo + the sorted lane).  DEFER: each is
+// recorded in View::fcopy for d1c_fusecopy - nothing in front of the ALT stage reads the fused bytes, only F_seq_off / F_seq_len, which
+// the refine kernel writes either way.  Otherwise copied here.
+template <bool DEFER>
+SNF_D void fuse_parts(const View& v, int lane, int64_t slot, bool p_act, int64_t p_src, int32_t p_len, int64_t p_dst) {
+  if constexpr (DEFER) { if (p_act && p_len > 0) v.fcopy[slot] = FuseDesc::make(p_src, p_len, p_dst); }
+  else wave_copy_parts(v, lane, p_act, p_src, p_len, p_dst);
+}
+
+// The recorded parts, copied: a wave per 64 slots of the table (grid-stride; the slots in use end at Counts::NF), the parts it finds four
+// at a time.  An entry is cleared as it is taken, so the table is all zero again when the kernel ends: the next pass of the handle - the
+// same pass replayed from its graph included - starts from an empty table, as the first one does (zeroed at upload).  An entry whose
+// bytes would not lie inside the pool is dropped (the refine kernels never write one: they check the reservation).
+__global__ void __launch_bounds__(SNF_WAVE) d1c_fusecopy(const View v, int64_t n_unused) {
+  const int lane = threadIdx.x;
+  int64_t n = v.cnt->NF; if (n > v.N) n = v.N;
+  for (int64_t base = (int64_t)blockIdx.x * SNF_WAVE; base < n; base += (int64_t)gridDim.x * SNF_WAVE) {
+    const int64_t s = base + lane;
+    FuseDesc d{0, 0};
+    if (s < n) d = v.fcopy[s];
+    const int32_t len = d.len();
+    if (__ballot(len != 0) == 0ull) continue;
+    if (len != 0) v.fcopy[s] = FuseDesc{0, 0};
+    const bool on = len > 0 && d.src() + len <= v.pool_cap && d.dst() + len <= v.pool_cap;
+    wave_copy_parts(v, lane, on, d.src(), on ? len : 0, d.dst());
   }
 }
 
@@ -145,7 +174,8 @@ struct WaveLds {
 #define SNF_RT(k) do { } while (0)
 #define SNF_RT_FLUSH() do { } while (0)
 #endif
-// one block = one wave = one merged cluster per loop iteration (grid-stride over clusters)
+// one block = one wave = one merged cluster per loop iteration (grid-stride over clusters); DEFER: fuse_parts
+template <bool DEFER>
 __global__ void __launch_bounds__(SNF_WAVE) d1w_refine(const View v, int64_t n_unused) {
   IT_SCOPE(5)
   __shared__ WaveLds lds;
@@ -269,7 +299,7 @@ __global__ void __launch_bounds__(SNF_WAVE) d1w_refine(const View v, int64_t n_u
         const int my_start = (act && (smask & upto)) ? 63 - __builtin_clzll(smask & upto) : 0;
         const bool p_act = act && __shfl((int)need_copy, my_start, SNF_WAVE) != 0;
         const int64_t p_dst = __shfl(new_off, my_start, SNF_WAVE) + (x_seq - __shfl(x_seq, my_start, SNF_WAVE));
-        wave_copy_parts(v, lane, p_act, s_seq_off, p_act ? s_seq_len : 0, p_dst);
+        fuse_parts<DEFER>(v, lane, (int64_t)lo + lane, p_act, s_seq_off, p_act ? s_seq_len : 0, p_dst);
       }
       const bool ok_seq = start && seq_ok && (nparts == 1 || need_copy);
       // compact the fused leads (start lanes) to lanes 0..m-1
@@ -287,7 +317,7 @@ __global__ void __launch_bounds__(SNF_WAVE) d1w_refine(const View v, int64_t n_u
       f_seq_off = __shfl(t_seq_off, src2, SNF_WAVE);
       }
     }
-    SNF_RT(3);   // pool reservation, byte copies, compaction
+    SNF_RT(3);   // pool reservation, byte copies (or their descriptors), compaction
     const bool fact = lane < m;
     if (fact) {
       v.F_orig[lo + lane] = f_orig; v.F_svlen[lo + lane] = f_svlen; v.F_lpos[lo + lane] = lo + f_lp;

@@ -30,7 +30,7 @@ template <int G> SNF_D int64_t gshfl_i64(int64_t x, int src, int gbase) { return
 
 struct GroupLds { int32_t perm[SNF_WAVE], seg_start[SNF_WAVE], seg_key[SNF_WAVE]; };
 
-template <int G>
+template <int G, bool DEFER>
 __global__ void __launch_bounds__(SNF_WAVE) d1g_refine(const View v, int64_t n_unused) {
   IT_SCOPE(4)
   static_assert(G == 8, "group width in use");
@@ -145,12 +145,12 @@ __global__ void __launch_bounds__(SNF_WAVE) d1g_refine(const View v, int64_t n_u
         new_off = pbase + (incl - mine);
         if (need_copy && new_off + tot_seq > v.pool_cap) { atomicOr(&v.cnt->overflow, 1); need_copy = false; }
       }
-      {  // the parts that are copied, as in d1w_refine (the copy itself is the wave's: all groups' parts, four at a time)
+      {  // the parts that are copied, as in d1w_refine (an in-place copy is the wave's: all groups' parts, four at a time)
         const unsigned long long upto = (2ull << gl) - 1ull;
         const int my_start = (fact0 && (smask & upto)) ? 63 - __builtin_clzll(smask & upto) : 0;      // (group-relative)
         const bool p_act = fact0 && __shfl((int)need_copy, gbase + my_start, SNF_WAVE) != 0;
         const int64_t p_dst = __shfl(new_off, gbase + my_start, SNF_WAVE) + (x_seq - __shfl(x_seq, gbase + my_start, SNF_WAVE));
-        wave_copy_parts(v, lane, p_act, s_seq_off, p_act ? s_seq_len : 0, p_dst);
+        fuse_parts<DEFER>(v, lane, (int64_t)lo + gl, p_act, s_seq_off, p_act ? s_seq_len : 0, p_dst);
       }
       const bool ok_seq = start && seq_ok && (nparts == 1 || need_copy);
       // compact the fused leads (start lanes) to the front of the group
