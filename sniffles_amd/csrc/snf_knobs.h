@@ -38,7 +38,9 @@ struct BatchKnobs {
   bool pf_spread = env_int("SNF_PF_SPREAD", 0) == 1; // SNF_PF_SPREAD=1: bitmap cells spread over L2 channels (measured: a1_keys 0.146 ms spread / 0.111 adjacent)
   bool winfront = !env_set("SNF_NO_WINFRONT");       // SNF_NO_WINFRONT (set): the sort path instead of the window front end (snf_stage_window.h)
   int win_bits = env_int("SNF_WIN_BITS", 0);         // SNF_WIN_BITS=k: window width forced to 2^k bins (6..win_bits_max; 0 / out of range: chosen from the data)
-  int win_bits_max = env_int("SNF_WIN_BITS_MAX", 10); // SNF_WIN_BITS_MAX=k, default 10: widest window tried (measured on the 30x genome: 10 beats 9 and 8)
+  int win_bits_max = [] { const int v = env_int("SNF_WIN_BITS_MAX", 10); return v >= 6 && v <= 12 ? v : 10; }();   // SNF_WIN_BITS_MAX=6..12, default 10 (anything
+                                                     //   else: 10): widest window tried (measured on the 30x genome: 10 beats 9 and 8).  12 is what win_pack's bin field
+                                                     //   holds (snf_stage_window.h), 6 the narrowest window do_upload sizes its arrays for (WIN_W_MIN)
   bool w4_split = env_on("SNF_W4_SPLIT");            // SNF_W4_SPLIT!=0: w4s_segment as its small instance + the large one over a list; default: one launch
   bool pool_slices = !env_set("SNF_NO_POOL_SLICES"); // SNF_NO_POOL_SLICES (set): fused sequences through the shared counter only; default: a private slice per resident wave
   int fuse_copy = env_set("SNF_FUSE_COPY") ? env_on("SNF_FUSE_COPY") : -1;   // SNF_FUSE_COPY=0/1: the parts of fused sequences copied inside the refine kernels / by d1c_fusecopy

@@ -997,7 +997,7 @@ void do_upload(snf_batch_impl* b) {
     return off[(size_t)T];
   };
   int64_t win_slots_max = 0;
-  const bool front_wanted = v.prefilter && v.wave_path && b->k.winfront && b->k.fuse && N <= ((int64_t)1 << 25);
+  const bool front_wanted = v.prefilter && v.wave_path && b->k.winfront && b->k.fuse && N <= ((int64_t)1 << 25) && T < (1 << 17);   // (wkey_make: 25 + 3 index bits; whead2: t * 8 + svtype in 20)
   if (front_wanted) {
     std::vector<int64_t> off;
     win_slots_max = win_layout(WIN_W_MIN, off);

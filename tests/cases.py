@@ -480,6 +480,23 @@ LADDERS["ladder_phased_mosaic"] = (case_ladder_phased, dict(_ALL_SEQ[0], mosaic=
 LADDERS["ladder_long_ins"] = (case_ladder_long_ins, dict(_ALL_SEQ[0]), _ALL_SEQ[1])
 
 
+# the window front end at its block, round, bin and layout borders (tests/window_cases.py builds the tables, tests/test_window_edges.py
+# asserts the layouts they were planned for); window_cases imports this module, hence the late imports
+def _window_table(name):
+    def build():
+        import window_cases
+        return getattr(window_cases, "table_" + name)()
+    return build
+
+
+WINDOW_EDGES = {
+    "window_edges_blocks_rounds": (_window_table("blocks_rounds"), {}, ()),
+    "window_edges_bins": (_window_table("bins"), {}, ()),
+    "window_edges_bins_mosaic": (_window_table("bins"), dict(mosaic=True), ("--mosaic",)),
+    "window_edges_borders": (_window_table("borders"), {}, ()),
+}
+
+
 HAND = {
     "resplit_wrap": (case_resplit_wrap, {}, ()),
     "merge_index_rule": (case_merge_index_rule, {}, ()),
@@ -504,6 +521,7 @@ HAND = {
     # RNAMES the reads of the whole cluster (sv.py:555 vs 636)
     "bnd_mixed_mates_no_resplit": (case_bnd_stale_end, dict(dev_no_resplit=True), ("--dev-no-resplit",)),
     **LADDERS,
+    **WINDOW_EDGES,
 }
 
 # seeded synthetic (SURVEY.md 8d shapes, shrunk contigs) --------------------------------------------

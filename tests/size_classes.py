@@ -4,7 +4,8 @@ tests/test_size_classes.py are derived from.  A threshold that is no longer foun
 silently tests the middle of a class is what this module is there to prevent.  ed_thresholds(): the same for the edit-distance
 kernels and the merge kernel that calls them (tests/ed_edges.py, tests/test_edit_distance_edges.py).  extract_thresholds(): the same
 for the extraction kernels (tests/extract_edges.py, tests/test_extract_edges.py).  coverage_thresholds(): the same for the read-table rank
-index, the coverage kernels on it and the genotype table (tests/coverage_cases.py, tests/test_coverage_edges.py, tests/test_genotype_edges.py)."""
+index, the coverage kernels on it and the genotype table (tests/coverage_cases.py, tests/test_coverage_edges.py, tests/test_genotype_edges.py).
+window_thresholds(): the same for the window front end and its packed fields (tests/window_cases.py, tests/test_window_edges.py)."""
 import os
 import re
 
@@ -152,6 +153,90 @@ def coverage_thresholds():
         gt_n=_define("SNF_GT_N", "snf_view.h"),
         wrap_depth=int(_one(r"if \(masked \|\| maxd\[\(size_t\)t\] >= (\d+) \|\| b->k\.cov_exact\)", lib_hip, "the uint16 wrap decision of the upload")),
     )
+
+
+def window_thresholds():
+    """dict of the literals of the window front end (snf_stage_window.h, the width choice of do_upload in snf_lib.hip, the two width
+    switches of snf_knobs.h): the largest instance, the widths tried, the 256 and 64 of the width / instance rule, the pad behind the
+    sort keys, and every shift and mask of the packed fields - the bin of a lead inside its window and `is_long` / `hap` next to it
+    (win_pack), the sort key (wkey_make), the high half of a key_out word, whead2 - with the relations between them the kernels rely
+    on.  A field that is written with one literal and read with another is an error here, like a literal that is no longer found."""
+    w, lib_hip, knobs = _src("snf_stage_window.h"), _src("snf_lib.hip"), _src("snf_knobs.h")
+    pack = _one(r"SNF_HD uint32_t win_pack\(const View& v, uint32_t bin_low, bool is_long, uint32_t hap\) \{ return bin_low \| "
+                r"\(\(is_long \? 1u : 0u\) << (\d+)\) \| \(hap << (\d+)\); \}", w, "win_pack")
+    unpack = (_one(r"SNF_HD uint32_t win_bin_low\(uint32_t a\) \{ return a & (0x[0-9a-f]+)u; \}", w, "win_bin_low"),
+              _one(r"SNF_HD bool win_is_long\(uint32_t a\) \{ return \(a >> (\d+)\) & 1u; \}", w, "win_is_long"),
+              _one(r"SNF_HD uint32_t win_hap\(uint32_t a\) \{ return \(a >> (\d+)\) & 3u; \}", w, "win_hap"))
+    key = _one(r"return \(\(uint64_t\)widx << (\d+)\) \| \(\(uint64_t\)win_bin_low\(a\) << (\d+)\) \| \(\(uint64_t\)\(uint32_t\)word << (\d+)\) \| "
+               r"\(\(uint64_t\)win_hap\(a\) << (\d+)\) \| \(win_is_long\(a\) \? 1ull : 0ull\);", w, "wkey_make")
+    unkey = (_one(r"wkey_group\(uint64_t k\) \{ return \(uint32_t\)\(k >> (\d+)\); \}", w, "wkey_group"),
+             _one(r"wkey_bin\(uint64_t k\) \{ return \(uint32_t\)\(k >> (\d+)\) & (0x[0-9a-f]+)u; \}", w, "wkey_bin"),
+             _one(r"wkey_widx\(uint64_t k\) \{ return \(uint32_t\)\(k >> (\d+)\); \}", w, "wkey_widx"),
+             _one(r"wkey_index\(uint64_t k\) \{ return \(uint32_t\)\(k >> (\d+)\); \}", w, "wkey_index"),
+             _one(r"wkey_hap\(uint64_t k\) \{ return \(uint32_t\)\(k >> (\d+)\) & 3u; \}", w, "wkey_hap"))
+    hi = _one(r"\(\(f_norm \? rn : rl\) << (\d+)\) \| \(\(uint32_t\)j << (\d+)\) \| \(f_seed \? rs << (\d+) : 0u\);", w, "the high half of key_out")
+    unhi = (_one(r"const int64_t owner = p / 64 - \(int64_t\)\(\(hi >> (\d+)\) & (\d+)u\);", w, "the owner of a position in w6t_emit"),
+            _one(r"const uint32_t rank = \(hi >> (\d+)\) & (0x[0-9a-f]+)u;", w, "the rank of a lead in w6t_emit"),
+            _one(r"const int64_t qs = \(int64_t\)v\.ws_seeds\[owner\] \+ \(hi >> (\d+)\);", w, "the seed rank in w6t_emit"))
+    h2 = _one(r"v\.whead2\[B0 \+ x\] = \(uint64_t\)\(uint32_t\)\(int32_t\)start \| \(\(uint64_t\)wG\[wl\] << (\d+)\) \| \(\(uint64_t\)\(f_norm \? rl : rn\) << (\d+)\);", w, "whead2")
+    unh2 = (_one(r"const uint32_t other = \(uint32_t\)\(h2 >> (\d+)\);", w, "the other offset in w6t_emit"),
+            _one(r"v\.seed_grp\[qs\] = \(int\)\(\(h2 >> (\d+)\) & (0x[0-9a-f]+)u\);", w, "seed_grp in w6t_emit"))
+    rows = _one(r"constexpr int CAPW = CAP \+ (\d+), E = CAPW / (\d+), PAD = (\d+);", w, "the rows of w4s_segment")
+    wmin = _one(r"const int WIN_W_MAX = b->k\.win_bits_max, WIN_W_MIN = (\d+);", lib_hip, "WIN_W_MIN")
+    wmax = _one(r'int win_bits_max = \[\] \{ const int v = env_int\("SNF_WIN_BITS_MAX", (\d+)\); return v >= (\d+) && v <= (\d+) \? v : (\d+); \}\(\);',
+                knobs, "the default and the range of SNF_WIN_BITS_MAX")
+    pick = _one(r"if \(hc\.max_win <= (\d+) \|\| \(best_w < 0 && hc\.max_win <= SNF_WIN_MAXCAP\)\) \{[^\n]*\n\s*if \(hc\.max_win <= (\d+)\) break;", lib_hip,
+                "the width rule of do_upload")
+    cap = _one(r"b->win_cap = best_max <= (\d+) \? (\d+) : best_max <= (\d+) \? (\d+) : SNF_WIN_MAXCAP;", lib_hip, "the instance rule of do_upload")
+    front = _one(r"const bool front_wanted = v\.prefilter && v\.wave_path && b->k\.winfront && b->k\.fuse && N <= \(\(int64_t\)1 << (\d+)\) && T < \(1 << (\d+)\);",
+                 lib_hip, "front_wanted")
+    t = dict(
+        win_maxcap=_define("SNF_WIN_MAXCAP", "snf_stage_window.h"), w_min=int(wmin), w_max_default=int(wmax[0]), w_max_lo=int(wmax[1]), w_max_hi=int(wmax[2]),
+        win_mid=int(pick[0]), win_small=int(cap[0]), pad=int(rows[2]),
+        long_shift=int(pack[0]), hap_shift=int(pack[1]), bin_mask=int(unpack[0], 16),
+        key_widx_shift=int(key[0]), key_bin_shift=int(key[1]), key_index_shift=int(key[2]), key_hap_shift=int(key[3]),
+        hi_rank_shift=int(hi[0]), hi_blk_shift=int(hi[1]), hi_seed_shift=int(hi[2]), hi_rank_mask=int(unhi[1][1], 16), hi_blk_mask=int(unhi[0][1]),
+        h2_grp_shift=int(h2[0]), h2_other_shift=int(h2[1]), h2_grp_mask=int(unh2[1][1], 16),
+        n_bits=int(front[0]), t_bits=int(front[1]),
+    )
+    same = [("the default of SNF_WIN_BITS_MAX and its fall-back", wmax[0], wmax[3]), ("the 256 of the width rule", pick[0], pick[1]),
+            ("the 256 of the instance rule", pick[0], cap[2]), ("the 256 of the instance rule", cap[2], cap[3]), ("the 64 of the instance rule", cap[0], cap[1]),
+            ("the rows of w4s_segment", rows[0], rows[1]), ("is_long", pack[0], unpack[1]), ("hap", pack[1], unpack[2]),
+            ("the bin of a key", key[1], unkey[0]), ("the bin of a key", key[1], unkey[1][0]), ("the bin mask", unpack[0], unkey[1][1]),
+            ("the window of a key", key[0], unkey[2]), ("the index of a key", key[2], unkey[3]), ("the hap of a key", key[3], unkey[4]),
+            ("the rank of a word", hi[0], unhi[1][0]), ("the block distance of a word", hi[1], unhi[0][0]), ("the seed rank of a word", hi[2], unhi[2]),
+            ("the group of whead2", h2[0], unh2[1][0]), ("the other offset of whead2", h2[1], unh2[0])]
+    for what, a, b in same:
+        if int(a, 0) != int(b, 0):
+            raise AssertionError(f"size_classes: {what} is written as two different numbers ({a}, {b})")
+    # ---- what the kernels rely on
+    top = WAVE - 1 + t["win_maxcap"]                       # the last position a wave of w4s_segment can own, relative to its block
+    rel = [
+        ("the bin mask is a run of low bits below is_long", t["bin_mask"] & (t["bin_mask"] + 1) == 0 and t["bin_mask"] + 1 == 1 << t["long_shift"]),
+        ("hap lies above is_long", t["hap_shift"] == t["long_shift"] + 1),
+        ("the widest admissible W fits the bin field", (1 << t["w_max_hi"]) - 1 <= t["bin_mask"]),
+        ("the widths tried begin at WIN_W_MIN", t["w_max_lo"] == t["w_min"] <= t["w_max_default"] <= t["w_max_hi"]),
+        ("the bin field of a key ends below the window", t["key_bin_shift"] + t["bin_mask"].bit_length() <= t["key_widx_shift"]),
+        ("the window index of a wave (64 windows) fits above it", t["key_widx_shift"] + 6 <= 64),
+        ("hap (2 bits) and is_long lie below the index", t["key_hap_shift"] == 1 and t["key_index_shift"] == t["key_hap_shift"] + 2),
+        ("25 + 3 index bits lie below the bin of a key", t["n_bits"] + t["key_index_shift"] <= t["key_bin_shift"]),
+        ("63 + SNF_WIN_MAXCAP fits the rank field", top <= t["hi_rank_mask"] and t["hi_rank_shift"] + t["hi_rank_mask"].bit_length() <= t["hi_blk_shift"]),
+        ("... and uint16_t (hpos, the counts of whead)", top < 1 << 16),
+        ("(63 + SNF_WIN_MAXCAP) / 64 fits the block-distance field", top // WAVE <= t["hi_blk_mask"] and
+         t["hi_blk_shift"] + t["hi_blk_mask"].bit_length() <= t["hi_seed_shift"] and t["hi_blk_mask"] & (t["hi_blk_mask"] + 1) == 0),
+        ("the seed-rank field holds 63 + SNF_WIN_MAXCAP", top < 1 << (32 - t["hi_seed_shift"])),
+        ("the flags lie below the rank", t["hi_rank_shift"] == 4),
+        ("the other offset of whead2 holds 63 + SNF_WIN_MAXCAP", top < 1 << (64 - t["h2_other_shift"])),
+        ("the group of whead2 lies between the start and the other offset", t["h2_grp_shift"] == 32 and
+         t["h2_grp_shift"] + t["h2_grp_mask"].bit_length() <= t["h2_other_shift"]),
+        ("t * 8 + svtype fits the group of whead2", (((1 << t["t_bits"]) - 1) * 8 + 7) <= t["h2_grp_mask"]),
+        ("the instances ascend", WAVE == t["win_small"] < t["win_mid"] == WIN_MID < t["win_maxcap"]),
+        ("the pad is a power of two that divides a block", t["pad"] & (t["pad"] - 1) == 0 and WAVE % t["pad"] == 0),
+    ]
+    for what, ok in rel:
+        if not ok:
+            raise AssertionError(f"size_classes: {what} - no longer true of the literals as read: {t}")
+    return t
 
 
 def ed_band_is_wide(t, m, n, k):
