@@ -824,6 +824,15 @@ typedef struct snf_bai_run_result {
 int snf_bai_run(snf_bgzf_t* z, const int64_t* member_file_off, const snf_bai_carry_t* in, snf_bai_run_result_t* out);
 const char* snf_bai_last_error(void);
 
+/* The same run for a CSI index (CSIv1) of any level scheme: bin = reg2bin(pos, end) over `depth` levels above windows of
+ * 2^min_shift bases (an interval that crosses 2^(min_shift + 3 depth) falls to bin 0), and win_off / win_index / win_min count
+ * windows of 2^min_shift bases: the caller's win_off table is built with the same shift.  Carry, result, refusals and their
+ * words are snf_bai_run's (snf_bai_last_error); with 14 / 5 every field equals what snf_bai_run returns.  SNF_BAI_THREAD and
+ * SNF_BAI_GRID select the forms as they do there.  Refused with a message, the handle stays usable: min_shift outside 8 .. 30,
+ * depth outside 1 .. 10, min_shift + 3 depth above 40.  Additive to ABI version 5. */
+int snf_csi_run(snf_bgzf_t* z, const int64_t* member_file_off, const snf_bai_carry_t* in, int32_t min_shift, int32_t depth,
+                snf_bai_run_result_t* out);
+
 /* -----------------------------------------------------------------------------------------------------------------
  * BGZF deflate on the device (csrc/snf_deflate.h): bytes + the caller's member cuts -> a run of complete BGZF members
  * (18-byte header with BSIZE, raw deflate with dynamic Huffman codes or one stored block, CRC-32, ISIZE) as one

@@ -450,7 +450,8 @@ class snf_bgzf_result_t(C.Structure):
                 ("d_rec_off", C.c_void_p), ("ms_inflate", C.c_float), ("ms_chain", C.c_float)]
 
 
-# ---- BAM index of a run (snf_bai_run, csrc/snf_bamindex.h)
+# ---- BAM index of a run (snf_bai_run, snf_csi_run: the same carry and result; csrc/snf_bamindex.h)
+CSI_MIN_SHIFT, CSI_DEPTH, CSI_TOP_BITS = (8, 30), (1, 10), 40      # what snf_csi_run accepts: min_shift, depth, min_shift + 3 depth
 class snf_bai_carry_t(C.Structure):
     _fields_ = [("count", i64), ("have_prev", i32), ("prev_ref", i32), ("prev_pos", i32), ("prev_bin", C.c_uint32), ("n_ref", i32),
                 ("_pad", i32), ("win_off", C.POINTER(C.c_int64))]

@@ -315,6 +315,15 @@ class BgzfDevice:
         """The index tables of the run the last `inflate` left in HBM (csrc/snf_bamindex.h).  `member_file_off`: n_members + 1
         (`member_file_offsets`); `win_off`: the first 16-kb window of every reference in one table, n_ref + 1; `carry`: the
         `snf_bai_carry_t` the run before returned, or None at the start of the file."""
+        return self._index_run(member_file_off, win_off, carry, None)
+
+    def csi_run(self, member_file_off: np.ndarray, win_off: np.ndarray, carry=None, min_shift: int = 14, depth: int = 5) -> dict:
+        """`bai_run` for a CSI of `depth` levels over windows of 2^min_shift bases (snf_csi_run): the bins follow
+        `bamindex.reg2bin(pos, end, min_shift, depth)`, `win_off` (`window_offsets(lens, min_shift)`), `win_index` and `win_min`
+        count windows of that size.  Parameters the entry point does not take are a ValueError; the handle stays usable."""
+        return self._index_run(member_file_off, win_off, carry, (int(min_shift), int(depth)))
+
+    def _index_run(self, member_file_off, win_off, carry, scheme) -> dict:
         import ctypes as C
         from . import abi
         foff = np.ascontiguousarray(member_file_off, np.int64)
@@ -323,9 +332,13 @@ class BgzfDevice:
         cin.n_ref = int(wo.shape[0] - 1)
         cin.win_off = wo.ctypes.data_as(C.POINTER(C.c_int64))
         r = abi.snf_bai_run_result_t()
-        if self.lib.snf_bai_run(self._h, foff.ctypes.data, C.byref(cin), C.byref(r)) != 0:
+        if scheme is None:
+            rc = self.lib.snf_bai_run(self._h, foff.ctypes.data, C.byref(cin), C.byref(r))
+        else:
+            rc = self.lib.snf_csi_run(self._h, foff.ctypes.data, C.byref(cin), scheme[0], scheme[1], C.byref(r))
+        if rc != 0:
             msg = self.lib.snf_bai_last_error().decode("utf-8", "replace")
-            if msg.startswith(("truncated BAM record", "BAM not coordinate-sorted")):
+            if msg.startswith(("truncated BAM record", "BAM not coordinate-sorted", "snf_csi_run: min_shift")):
                 raise ValueError(msg)
             raise self._err(msg)
         n, k, w = int(r.n_records), int(r.n_runs), int(r.n_windows)
@@ -483,10 +496,11 @@ def bam_device(data: bytes, device: int = 0) -> DeviceBamRecords:
 
 
 # ------------------------------------------------------------------------------------------------- indexed access
-def window_offsets(ref_lens) -> np.ndarray:
-    """int64[n_ref + 1]: the first 16-kb window of every reference in one table (a reference of no bases has one window)."""
+def window_offsets(ref_lens, min_shift: int = 14) -> np.ndarray:
+    """int64[n_ref + 1]: the first window of 2^min_shift bases (16 kb) of every reference in one table (a reference of no bases
+    has one window)."""
     off = np.zeros(len(ref_lens) + 1, np.int64)
-    np.cumsum([((max(int(n), 1) - 1) >> 14) + 1 for n in ref_lens], out=off[1:])
+    np.cumsum([((max(int(n), 1) - 1) >> min_shift) + 1 for n in ref_lens], out=off[1:])
     return off
 
 
@@ -500,13 +514,16 @@ def _map_file(path: str):
 
 
 class _IndexTables:
-    """What the runs of `index_bam` add up to: chunks per (reference, bin) in file order, the window minima, the counts."""
+    """What the runs of `index_bam` add up to: chunks per (reference, bin) in file order, the window minima, the counts.
+    `scheme`: None for a BAI, (min_shift, depth) for a CSI - the windows are then 2^min_shift bases and `finish` turns the
+    minima into the bins' loffset values."""
 
-    def __init__(self, ref_lens):
+    def __init__(self, ref_lens, scheme=None):
         from . import bamindex
         self.ref_lens = [int(x) for x in ref_lens]
+        self.scheme = scheme
         n_ref = len(self.ref_lens)
-        self.win_off = window_offsets(self.ref_lens)
+        self.win_off = window_offsets(self.ref_lens, 14 if scheme is None else scheme[0])
         self.lin = np.full(int(self.win_off[-1]), bamindex.U64_MAX, np.uint64)
         self.chunks = {}
         self.mapped, self.unmapped = np.zeros(n_ref, np.int64), np.zeros(n_ref, np.int64)
@@ -549,8 +566,13 @@ class _IndexTables:
             seg = bamindex.fill_linear(seg[:int(known[-1]) + 1]) if known.shape[0] else np.zeros(0, np.uint64)
             bins = {bn: np.array(ch, np.uint64).reshape(-1, 2) for (rf, bn), ch in self.chunks.items() if rf == i}
             meta = (self.off_beg[i], self.off_end[i], int(self.mapped[i]), int(self.unmapped[i])) if self.off_beg[i] is not None else None
-            refs.append(bamindex.RefIndex(bins=bins, linear=seg, meta=meta))
-        return bamindex.BamIndex(refs, self.n_no_coor, "bai", ref_lens=self.ref_lens)
+            if self.scheme is None:
+                refs.append(bamindex.RefIndex(bins=bins, linear=seg, meta=meta))
+            else:
+                refs.append(bamindex.RefIndex(bins=bins, loffset=bamindex.csi_loffsets(bins, seg, self.scheme[1]), meta=meta))
+        if self.scheme is None:
+            return bamindex.BamIndex(refs, self.n_no_coor, "bai", ref_lens=self.ref_lens)
+        return bamindex.BamIndex(refs, self.n_no_coor, "csi", self.scheme[0], self.scheme[1], ref_lens=self.ref_lens)
 
 
 def _next_run(r: dict, n_use: int, members: np.ndarray, foff: np.ndarray, carry, count: int):
@@ -568,20 +590,27 @@ def _next_run(r: dict, n_use: int, members: np.ndarray, foff: np.ndarray, carry,
     return int(foff[m]), abi.snf_bam_carry_t(skip=p - at, count=count, stream_pos=int(carry.stream_pos) + at, origin=origin, n_part=0), at
 
 
-def index_bam(path: str, out: str = None, device: int = 0, run_bytes: int = 256 << 20, stats: dict = None):
-    """The BAI of a coordinate-sorted BAM, built on the GPU (csrc/snf_bamindex.h); written to `out` if given.  The file is
+def index_bam(path: str, out: str = None, device: int = 0, run_bytes: int = 256 << 20, stats: dict = None, fmt: str = "bai", min_shift: int = 14):
+    """The BAI (`fmt="bai"`) or CSI (`fmt="csi"`) of a coordinate-sorted BAM, built on the GPU (csrc/snf_bamindex.h); written to
+    `out` if given.  A CSI has windows of 2^min_shift bases and as many levels as the longest reference of the header needs
+    (`bamindex.csi_depth`, at least 1): it holds references beyond 2^29 bases, which a BAI cannot.  The file is
     memory-mapped and goes through in runs of members of at most `run_bytes` compressed bytes: `BgzfDevice.inflate`, then
     `BgzfDevice.bai_run`; the host merges the tables of the runs (`_IndexTables`).  A run usually ends inside a record: that record
     is left out of the run and the next run starts at the member that holds its first byte (`_next_run`); a record larger than a
     run grows the run.  Refuses what htslib refuses: a file that is not coordinate-sorted (ValueError, naming the first offending
     record).  `stats`: filled with the number of runs, the kernel times and the byte counts."""
     from . import abi, bamindex
+    if fmt not in ("bai", "csi"):
+        raise ValueError(f"index_bam: fmt {fmt!r} is neither 'bai' nor 'csi'")
+    if fmt == "csi" and not abi.CSI_MIN_SHIFT[0] <= int(min_shift) <= abi.CSI_MIN_SHIFT[1]:
+        raise ValueError(f"index_bam: min_shift {min_shift} outside {abi.CSI_MIN_SHIFT[0]} .. {abi.CSI_MIN_SHIFT[1]}")
     data = _map_file(path)
     z = None
     try:
         names, lens, hlen = leading_header(data)
         size = len(data)
-        tables = _IndexTables(lens)
+        scheme = None if fmt == "bai" else (int(min_shift), max(1, bamindex.csi_depth(max([int(x) for x in lens] + [0]), int(min_shift))))
+        tables = _IndexTables(lens, scheme)
         z = BgzfDevice(device)
         fo, budget = 0, max(1, int(run_bytes))
         carry = abi.snf_bam_carry_t(skip=hlen, count=0, stream_pos=0, origin=hlen, n_part=0)
@@ -609,7 +638,7 @@ def index_bam(path: str, out: str = None, device: int = 0, run_bytes: int = 256 
             if cut and n_use == 0:                    # not one whole record (or the header) in this run: a longer one from the same place
                 budget *= 2
                 continue
-            b = z.bai_run(foff, tables.win_off, bcarry)
+            b = z.bai_run(foff, tables.win_off, bcarry) if scheme is None else z.csi_run(foff, tables.win_off, bcarry, *scheme)
             assert b["n"] == n_use
             tables.add_run(b, r["heads"][:n_use])
             bcarry = b["carry"]
@@ -627,7 +656,7 @@ def index_bam(path: str, out: str = None, device: int = 0, run_bytes: int = 256 
         if stats is not None:
             stats.update(info)
         if out is not None:
-            bamindex.write_bai(index, out)
+            (bamindex.write_bai if scheme is None else bamindex.write_csi)(index, out)
         return index
     finally:
         if z is not None:

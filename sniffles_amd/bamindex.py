@@ -1,4 +1,4 @@
-"""BAM indexes on the host: BAI and CSI read, queried and (BAI) written - SAM specification sections 5.2 and 5.3, CSIv1.
+"""BAM indexes on the host: BAI and CSI read, queried and written - SAM specification sections 5.2 and 5.3, CSIv1.
 
 The reference requires an index (`sniffles:172`, `check_index`), takes `bam.mapped` and the per-contig counts from it
 (`sniffles:298`, `317`) and reads every task's records with `bam.fetch(contig, start, end)` (`leadprov.py:488`) - all of it
@@ -269,5 +269,82 @@ def bai_bytes(index: BamIndex) -> bytes:
 
 def write_bai(index: BamIndex, path: str) -> None:
     data = bai_bytes(index)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+# ------------------------------------------------------------------------------------------------------------- CSI, written
+CSI_META_LOFFSET = 0      # the loffset htslib stores with the metadata pseudo-bin (hts_idx_finish / update_loff: a bin beyond the real ones)
+
+
+def csi_depth(max_ref_len: int, min_shift: int = 14) -> int:
+    """The smallest depth with 2^(min_shift + 3 depth) >= max_ref_len + 256: htslib's rule (sam_index_build, tbx_index_build),
+    5 for the human genome at min_shift 14.  A reference of a few bases gives 0; the device entry point takes 1 .. 10."""
+    need, depth = int(max_ref_len) + 256, 0
+    while need > 1 << (min_shift + 3 * depth):
+        depth += 1
+    return depth
+
+
+def bin_first_window(bins, depth: int) -> np.ndarray:
+    """int64[k]: the first min_shift window of every bin (htslib hts_bin_bot); `bins` are real bins of `depth` levels."""
+    b = np.asarray(bins, np.int64)
+    first = np.array([((1 << (3 * l)) - 1) // 7 for l in range(depth + 2)], np.int64)      # first bin of every level, and one past the last
+    level = np.searchsorted(first, b, side="right") - 1
+    return (b - first[level]) << (3 * (depth - level))
+
+
+def csi_loffsets(bins, filled: np.ndarray, depth: int) -> dict:
+    """bin -> loffset by htslib's update_loff.  `filled`: the window minima of the reference at min_shift granularity, cut behind
+    the last known window, holes filled with the following window's value (`fill_linear`).  A bin takes the value at its first
+    window, 0 if that window lies behind the array."""
+    b = sorted(int(x) for x in bins)
+    if not b:
+        return {}
+    w = bin_first_window(b, depth)
+    inside = w < filled.shape[0]
+    val = np.zeros(len(b), np.uint64)
+    val[inside] = filled[w[inside]]
+    return dict(zip(b, val.tolist()))
+
+
+def csi_raw(index: BamIndex) -> bytes:
+    """The inflated bytes of a CSIv1 file: magic, min_shift, depth, l_aux + aux, n_ref; per reference the bins in ascending order
+    with loffset and chunks, the metadata pseudo-bin last; n_no_coor."""
+    ms, depth = int(index.min_shift), int(index.depth)
+    if ms < 0 or depth < 0 or depth > 10:
+        raise ValueError(f"CSI: min_shift {ms} / depth {depth} out of range")
+    mb = meta_bin(depth)
+    aux = bytes(index.aux or b"")
+    out = [b"CSI\x01", struct.pack("<iii", ms, depth, len(aux)), aux, struct.pack("<i", index.n_ref)]
+    for i, r in enumerate(index.refs):
+        if r.bins and r.loffset is None:
+            raise ValueError(f"CSI: reference {i} has no loffset table (an index read from a BAI does not carry one)")
+        out.append(struct.pack("<i", len(r.bins) + (1 if r.meta is not None else 0)))
+        for b in sorted(r.bins):
+            if b >= mb:
+                raise ValueError(f"CSI: bin {b} of reference {i} is beyond the last bin of depth {depth}")
+            ch = np.ascontiguousarray(r.bins[b], "<u8")
+            out += [struct.pack("<IQi", b, int(r.loffset[b]), ch.shape[0]), ch.tobytes()]
+        if r.meta is not None:
+            out.append(struct.pack("<IQi4Q", mb, CSI_META_LOFFSET, 2, *[int(x) for x in r.meta]))
+    out.append(struct.pack("<Q", int(index.n_no_coor)))
+    return b"".join(out)
+
+
+def csi_bytes(index: BamIndex, deflater=None) -> bytes:
+    """A CSIv1 file: `csi_raw` as BGZF members of at most 0xff00 bytes and the EOF member, as htslib writes it.  The members come
+    from the host's zlib; `deflater`: a `bgzfout.DeflateDevice` that compresses them on the GPU instead."""
+    raw = csi_raw(index)
+    if deflater is None:
+        from . import bam
+        return bam.bgzf_deflate(raw, 6)
+    from . import bgzfout
+    image, _ = deflater.compress(raw)
+    return image + bgzfout.EOF_MEMBER
+
+
+def write_csi(index: BamIndex, path: str, deflater=None) -> None:
+    data = csi_bytes(index, deflater)
     with open(path, "wb") as f:
         f.write(data)

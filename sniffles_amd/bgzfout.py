@@ -152,9 +152,9 @@ _END = re.compile(rb"(?:^|;)END=(\d+)(?:;|$)")
 TBI_META_BIN = bamindex.meta_bin(5)
 
 
-def vcf_interval(line: bytes, number: int):
+def vcf_interval(line: bytes, number: int, tbi: bool = True):
     """(contig, beg, end) of a VCF record line as tabix's VCF preset takes it: beg = POS - 1, end = beg + len(REF), an INFO END=
-    greater than beg instead."""
+    greater than beg instead.  `tbi`: refuse what a `.tbi` cannot reach (a `.csi` has as many levels as the positions need)."""
     f = line.split(b"\t", 8)
     if len(f) < 8:
         raise ValueError(f"VCF line {number}: {len(f)} columns, a record has at least 8")
@@ -168,7 +168,7 @@ def vcf_interval(line: bytes, number: int):
     if m and int(m.group(1)) > beg:
         end = int(m.group(1))
     end = max(end, beg + 1)
-    if end > 1 << 29:
+    if tbi and end > 1 << 29:
         raise ValueError(f"VCF line {number}: position {end} is beyond 2^29, the last base a tabix index reaches")
     return f[0], beg, end
 
@@ -176,10 +176,15 @@ def vcf_interval(line: bytes, number: int):
 class VcfGzWriter(BgzfWriter):
     """A BgzfWriter for VCF text that writes `path + ".tbi"` on close().  Usable as the `vcf_handle` of pipeline.call_sample /
     combine / genotype_vcf.  The records must be sorted: a position that decreases inside a contig, or a contig that returns
-    after another one, is a ValueError naming the line (the reference refuses `.gz` with `--no-sort` for this reason)."""
+    after another one, is a ValueError naming the line (the reference refuses `.gz` with `--no-sort` for this reason).
+    `index="csi"` writes `path + ".csi"` instead - tabix over CSIv1 (what `pysam.tabix_index(csi=True)` writes), min_shift 14,
+    at least 5 levels and as many as the largest end needs: positions beyond 2^29 are accepted."""
 
-    def __init__(self, path: str, device: int = 0, run_bytes: int = 64 << 20, deflater: DeflateDevice = None):
+    def __init__(self, path: str, device: int = 0, run_bytes: int = 64 << 20, deflater: DeflateDevice = None, index: str = "tbi"):
+        if index not in ("tbi", "csi"):
+            raise ValueError(f"VcfGzWriter: index {index!r} is neither 'tbi' nor 'csi'")
         super().__init__(path, device, run_bytes, deflater)
+        self.index = index
         self._tail = b""
         self._upos = 0           # uncompressed offset of the start of the pending line
         self._line = 0
@@ -200,7 +205,7 @@ class VcfGzWriter(BgzfWriter):
         self._upos += size
         if not ln or ln.startswith(b"#"):
             return
-        name, beg, end = vcf_interval(ln, self._line)
+        name, beg, end = vcf_interval(ln, self._line, self.index == "tbi")
         tid = self._seen.get(name)
         if tid is None:
             tid = self._seen[name] = len(self._names)
@@ -253,10 +258,44 @@ class VcfGzWriter(BgzfWriter):
         out.append(struct.pack("<Q", 0))      # n_no_coor
         return b"".join(out)
 
+    def csi_index(self) -> bamindex.BamIndex:
+        """The index of what was written (after close()) as tabix over CSI: the intervals and virtual offsets of `index_bytes`,
+        bins of min_shift 14 and the depth the largest end needs (at least 5), the bins' loffset by htslib's rule
+        (`bamindex.csi_loffsets`), the tabix header of the VCF preset and the names as the aux block."""
+        names = b"".join(n + b"\0" for n in self._names)
+        depth, top = 5, max([r[2] for r in self._rec] + [0])
+        while top > 1 << (14 + 3 * depth):
+            depth += 1
+        per = [[] for _ in self._names]
+        for r in self._rec:
+            per[r[0]].append(r)
+        refs = []
+        for recs in per:
+            bins, prev = {}, None
+            lin = np.full(((max(r[2] for r in recs) - 1) >> 14) + 1, bamindex.U64_MAX, np.uint64)
+            for _, beg, end, us, ue in recs:
+                b = bamindex.reg2bin(beg, end, 14, depth)
+                vb, ve = self._voff(us), self._voff(ue)
+                if b == prev:
+                    bins[b][-1][1] = ve
+                else:
+                    bins.setdefault(b, []).append([vb, ve])
+                prev = b
+                w0, w1 = beg >> 14, (end - 1) >> 14
+                lin[w0:w1 + 1] = np.minimum(lin[w0:w1 + 1], np.uint64(vb))
+            bins = {b: np.array(ch, np.uint64) for b, ch in bins.items()}
+            refs.append(bamindex.RefIndex(bins=bins, loffset=bamindex.csi_loffsets(bins, bamindex.fill_linear(lin), depth),
+                                          meta=(self._voff(recs[0][3]), self._voff(recs[-1][4]), len(recs), 0)))
+        aux = struct.pack("<7i", 2, 1, 2, 0, ord("#"), 0, len(names)) + names
+        return bamindex.BamIndex(refs, 0, "csi", 14, depth, aux)
+
     def _finish(self) -> None:
         if self._tail:      # (a last line without its newline)
             self._one(self._tail, len(self._tail))
             self._tail = b""
+        if self.index == "csi":
+            bamindex.write_csi(self.csi_index(), self.path + ".csi", deflater=self._z)
+            return
         raw = self.index_bytes()
         image, _ = self._z.compress(raw)
         with open(self.path + ".tbi", "wb") as f:

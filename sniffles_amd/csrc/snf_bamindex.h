@@ -1,5 +1,5 @@
-// snf_bamindex.h - a BAM index (BAI, SAM specification 5.2) from the records an snf_bgzf_t holds after snf_bgzf_inflate: the inflated
-// stream, d_rec_off and the member table; the host adds one column, the file offset of every member.
+// snf_bamindex.h - a BAM index (BAI, SAM specification 5.2; CSIv1 for any min_shift / depth) from the records an snf_bgzf_t holds after
+// snf_bgzf_inflate: the inflated stream, d_rec_off and the member table; the host adds one column, the file offset of every member.
 //
 // Reference counterpart: the index pysam / htslib require behind `bam.fetch` (sniffles:172 check_index, leadprov.py:488) - htslib's
 // hts_idx_push / bam_endpos / hts_reg2bin; the host form of the same rules is tests/bam_index_cases.py.  Included from snf_extract.hip
@@ -19,6 +19,11 @@
 //                with the carry); unplaced records (refID -1) open none.  Then rocPRIM's exclusive scan, bai_compact (the opening
 //                records -> key refID << 32 | bin), a stable 64-bit radix sort (a bin's chunks stay in file order) and bai_table
 //                (key, first byte of the chunk's first record, end of its last one).
+//   csi_span / csi_linear   the same two bodies with the level scheme as run-time values of the view (snf_csi_run): the bin by
+//                csi_reg2bin - a loop of `depth` rounds over the levels from the deepest upwards, 64-bit shifts and compares in
+//                registers - and the windows at min_shift granularity.  The bai_* kernels are the instances with the literals 14 / 5;
+//                flag, scan, compact, sort and table do not know the levels and serve both (a bin of depth 10 is below 2^31: the key
+//                refID << 32 | bin holds it).
 // No kernel here waits for another workgroup: what depends on a predecessor's result (the bin) is a kernel of its own.
 #pragma once
 
@@ -36,6 +41,7 @@ struct BaiView {
   int64_t* flag; int64_t* run_idx; int64_t* run_start; unsigned long long* key; uint32_t* val;
   const unsigned long long* skey; const uint32_t* sval; unsigned long long* table; int64_t n_runs, n_placed;
   int32_t prev_ref, prev_pos; uint32_t prev_bin; int32_t have_prev;
+  int32_t min_shift, depth;              // the CSI instances only: the level scheme of the run (the BAI instances never read them)
 };
 
 // SAM specification 5.3, min_shift 14 / depth 5; the interval is [beg, end)
@@ -46,6 +52,17 @@ SNF_HD uint32_t bai_reg2bin(int64_t beg, int64_t end) {
   if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
   if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
   if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+  return 0;
+}
+// CSIv1, any min_shift / depth: the levels from the deepest upwards (bamindex.reg2bin); depth rounds on 64 bits, no memory access.  An
+// interval that crosses 2^(min_shift + 3 depth) meets no level and falls to bin 0; with 14 / 5 this is bai_reg2bin value for value.
+SNF_HD uint32_t csi_reg2bin(int64_t beg, int64_t end, int min_shift, int depth) {
+  --end;
+  int s = min_shift; int64_t t = ((1ll << (3 * depth)) - 1) / 7;
+  for (int l = depth; l > 0; --l) {
+    if (beg >> s == end >> s) return (uint32_t)(t + (beg >> s));
+    s += 3; t -= 1ll << (3 * (l - 1));
+  }
   return 0;
 }
 // stream position p in [0, stream_len] -> virtual offset: the last member whose output starts at or before p (behind the run: foff[n_mem])
@@ -61,7 +78,7 @@ SNF_HD unsigned long long bai_voff(const BaiView& v, int64_t p) {
 }
 SNF_HD void bai_error(const BaiView& v, int64_t rec, uint32_t code) { atomicMin(v.err, ((unsigned long long)rec << 4) | code); }
 
-template <bool WAVE> SNF_HD void bai_span_rec(int64_t i, const BaiView& v) {
+template <bool WAVE, bool CSI> SNF_HD void bai_span_rec(int64_t i, const BaiView& v) {
   const int lane = x_lane<WAVE>();
   const int64_t p = v.rec_off[i] + v.rel;
   int64_t end = 0; uint32_t bin = 0, code = BI_OK; unsigned long long vb = 0, ve = 0;
@@ -88,7 +105,7 @@ template <bool WAVE> SNF_HD void bai_span_rec(int64_t i, const BaiView& v) {
         for (int k = 0; k < n_cig; k++) { const uint32_t c = ld_u32(cig + 4 * (int64_t)k); if ((X_REFC >> (c & 15u)) & 1u) sum += c >> 4; }
       }
       end = (sum == 0 || (flag & 0x4u)) ? (int64_t)pos + 1 : (int64_t)pos + (int64_t)sum;
-      bin = bai_reg2bin(pos, end);
+      if constexpr (CSI) bin = csi_reg2bin(pos, end, v.min_shift, v.depth); else bin = bai_reg2bin(pos, end);
       vb = bai_voff(v, p); ve = bai_voff(v, rec_end);
       // sortedness: against the record before (the first record's predecessor is the carry's)
       int32_t pref = v.prev_ref, ppos = v.prev_pos; bool have = v.have_prev != 0;
@@ -107,30 +124,41 @@ template <bool WAVE> SNF_HD void bai_span_rec(int64_t i, const BaiView& v) {
   }
 }
 __global__ void __launch_bounds__(64) bai_span_wave(const BaiView v, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x; i < n; i += (int64_t)gridDim.x) bai_span_rec<true>(i, v);
+  for (int64_t i = (int64_t)blockIdx.x; i < n; i += (int64_t)gridDim.x) bai_span_rec<true, false>(i, v);
 }
-SNF_HD void bai_span_thread_body(int64_t i, const BaiView& v) { bai_span_rec<false>(i, v); }
+SNF_HD void bai_span_thread_body(int64_t i, const BaiView& v) { bai_span_rec<false, false>(i, v); }
 SNF_KERNEL(bai_span_thread, BaiView)
+__global__ void __launch_bounds__(64) csi_span_wave(const BaiView v, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x; i < n; i += (int64_t)gridDim.x) bai_span_rec<true, true>(i, v);
+}
+SNF_HD void csi_span_thread_body(int64_t i, const BaiView& v) { bai_span_rec<false, true>(i, v); }
+SNF_KERNEL(csi_span_thread, BaiView)
 
-template <bool WAVE> SNF_HD void bai_linear_rec(int64_t i, const BaiView& v) {
+template <bool WAVE, bool CSI> SNF_HD void bai_linear_rec(int64_t i, const BaiView& v) {
   const uint32_t st = v.sorted[i];
   if (st == BI_TRUNCATED || st == BI_REFID) return;
   const uint8_t* R = v.stream + v.rec_off[i] + v.rel;
   const int32_t ref = (int32_t)ld_u32(R + 4), pos = (int32_t)ld_u32(R + 8);
   if (ref < 0 || ((ld_u32(R + 16) >> 16) & 0x4u)) return;
   const int64_t end = v.end[i], nw = v.win_off[ref + 1] - v.win_off[ref];
-  const int64_t w0 = (pos > 0 ? (int64_t)pos : 0) >> 14;
-  int64_t w1 = ((end > 1 ? end : 1) - 1) >> 14;
+  const int sh = CSI ? v.min_shift : 14;      // (win_off is the caller's table at the same shift)
+  const int64_t w0 = (pos > 0 ? (int64_t)pos : 0) >> sh;
+  int64_t w1 = ((end > 1 ? end : 1) - 1) >> sh;
   if (w1 >= nw) w1 = nw - 1;      // (a record beyond the header's length of its reference: the table ends there)
   const unsigned long long vb = v.vbeg[i];
   unsigned long long* L = v.lin + v.win_off[ref];
   for (int64_t w = w0 + x_lane<WAVE>(); w <= w1; w += WAVE ? 64 : 1) atomicMin(&L[w], vb);
 }
 __global__ void __launch_bounds__(64) bai_linear_wave(const BaiView v, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x; i < n; i += (int64_t)gridDim.x) bai_linear_rec<true>(i, v);
+  for (int64_t i = (int64_t)blockIdx.x; i < n; i += (int64_t)gridDim.x) bai_linear_rec<true, false>(i, v);
 }
-SNF_HD void bai_linear_thread_body(int64_t i, const BaiView& v) { bai_linear_rec<false>(i, v); }
+SNF_HD void bai_linear_thread_body(int64_t i, const BaiView& v) { bai_linear_rec<false, false>(i, v); }
 SNF_KERNEL(bai_linear_thread, BaiView)
+__global__ void __launch_bounds__(64) csi_linear_wave(const BaiView v, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x; i < n; i += (int64_t)gridDim.x) bai_linear_rec<true, true>(i, v);
+}
+SNF_HD void csi_linear_thread_body(int64_t i, const BaiView& v) { bai_linear_rec<false, true>(i, v); }
+SNF_KERNEL(csi_linear_thread, BaiView)
 
 // ---- chunk runs: flag, (scan), compact, (sort), table -------------------------------------------------------------------
 SNF_HD void bai_flag_body(int64_t i, const BaiView& v) {      // n + 1 threads: flag[n] = 0 so that run_idx[n] is the number of runs

@@ -1618,7 +1618,9 @@ void do_bgzf_inflate(snf_bgzf* z, const uint8_t* comp, int64_t comp_len, const s
 }
 
 // ---- BAM index of the run (snf_bamindex.h)
-void do_bai_run(snf_bgzf* z, const int64_t* foff, const snf_bai_carry_t* cin, snf_bai_run_result_t* out) {
+// `csi`: the level scheme comes from min_shift / depth (snf_csi_run, the csi_* instances); otherwise the literals 14 / 5
+void do_bai_run(snf_bgzf* z, const int64_t* foff, const snf_bai_carry_t* cin, snf_bai_run_result_t* out, bool csi = false, int32_t min_shift = 14,
+                int32_t depth = 5) {
   if (!foff || !cin || !out) snf::fail("snf_bai_run: null argument");
   if (!z->have) snf::fail("snf_bai_run before a successful snf_bgzf_inflate");
   if (cin->n_ref < 0 || !cin->win_off) snf::fail("snf_bai_run: window table missing");
@@ -1640,6 +1642,7 @@ void do_bai_run(snf_bgzf* z, const int64_t* foff, const snf_bai_carry_t* cin, sn
   v.lin = x_alloc<unsigned long long>(pool, (size_t)n_win); v.win_off = x_up(pool, cin->win_off, (size_t)cin->n_ref + 1); v.n_ref = cin->n_ref;
   v.flag = x_alloc<int64_t>(pool, N1); v.run_idx = x_alloc<int64_t>(pool, N1);
   v.prev_ref = cin->prev_ref; v.prev_pos = cin->prev_pos; v.prev_bin = cin->prev_bin; v.have_prev = cin->have_prev;
+  v.min_shift = min_shift; v.depth = depth;
   const unsigned long long none[2] = {~0ull, ~0ull};
   x_h2d(v.err, none, 16);
   SNF_HIP(hipMemset(v.lin, 0xff, (size_t)(n_win ? n_win : 1) * 8));
@@ -1648,7 +1651,10 @@ void do_bai_run(snf_bgzf* z, const int64_t* foff, const snf_bai_carry_t* cin, sn
   // (every bracket holds launches only: the copies to the host and the host's waits lie between the brackets)
   SNF_HIP(hipEventRecord(z->bev[0], 0));
   if (n) {
-    if (k.thread_form) hipLaunchKernelGGL(bai_span_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
+    if (csi) {
+      if (k.thread_form) hipLaunchKernelGGL(csi_span_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
+      else hipLaunchKernelGGL(csi_span_wave, dim3(grid_w), dim3(64), 0, 0, v, n);
+    } else if (k.thread_form) hipLaunchKernelGGL(bai_span_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
     else hipLaunchKernelGGL(bai_span_wave, dim3(grid_w), dim3(64), 0, 0, v, n);
     SNF_HIP(hipGetLastError());
   }
@@ -1674,7 +1680,10 @@ void do_bai_run(snf_bgzf* z, const int64_t* foff, const snf_bai_carry_t* cin, sn
   void* scan_tmp = x_alloc<uint8_t>(pool, scan_need);
   SNF_HIP(hipEventRecord(z->bev[2], 0));
   if (n) {
-    if (k.thread_form) hipLaunchKernelGGL(bai_linear_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
+    if (csi) {
+      if (k.thread_form) hipLaunchKernelGGL(csi_linear_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
+      else hipLaunchKernelGGL(csi_linear_wave, dim3(grid_w), dim3(64), 0, 0, v, n);
+    } else if (k.thread_form) hipLaunchKernelGGL(bai_linear_thread, dim3(grid_t), dim3(256), 0, 0, v, n);
     else hipLaunchKernelGGL(bai_linear_wave, dim3(grid_w), dim3(64), 0, 0, v, n);
     SNF_HIP(hipGetLastError());
   }
@@ -1777,6 +1786,19 @@ int snf_bai_run(snf_bgzf_t* z, const int64_t* member_file_off, const snf_bai_car
   if (!z) { g_berr = "null handle"; return 1; }
   if (hipSetDevice(z->device) != hipSuccess) { g_berr = "hipSetDevice failed"; return 1; }
   try { do_bai_run(z, member_file_off, in, out); }
+  catch (const snf::Error& e) { g_berr = e.msg; return 1; }
+  catch (const std::exception& e) { g_berr = e.what(); return 1; }
+  return 0;
+}
+int snf_csi_run(snf_bgzf_t* z, const int64_t* member_file_off, const snf_bai_carry_t* in, int32_t min_shift, int32_t depth, snf_bai_run_result_t* out) {
+  if (!z) { g_berr = "null handle"; return 1; }
+  if (min_shift < 8 || min_shift > 30 || depth < 1 || depth > 10 || min_shift + 3 * depth > 40) {
+    g_berr = "snf_csi_run: min_shift " + std::to_string(min_shift) + " / depth " + std::to_string(depth) +
+             " out of range (min_shift 8..30, depth 1..10, min_shift + 3 depth at most 40)";
+    return 1;
+  }
+  if (hipSetDevice(z->device) != hipSuccess) { g_berr = "hipSetDevice failed"; return 1; }
+  try { do_bai_run(z, member_file_off, in, out, true, min_shift, depth); }
   catch (const snf::Error& e) { g_berr = e.msg; return 1; }
   catch (const std::exception& e) { g_berr = e.what(); return 1; }
   return 0;

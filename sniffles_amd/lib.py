@@ -101,6 +101,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.snf_bgzf_last_error.restype = C.c_char_p
     lib.snf_bai_run.argtypes = [vp, C.c_void_p, C.POINTER(abi.snf_bai_carry_t), C.POINTER(abi.snf_bai_run_result_t)]
     lib.snf_bai_run.restype = C.c_int
+    lib.snf_csi_run.argtypes = [vp, C.c_void_p, C.POINTER(abi.snf_bai_carry_t), C.c_int32, C.c_int32, C.POINTER(abi.snf_bai_run_result_t)]
+    lib.snf_csi_run.restype = C.c_int
     lib.snf_bai_last_error.restype = C.c_char_p
     for f in ("snf_extract_attach_device", "snf_bgzf_create", "snf_bgzf_inflate", "snf_bgzf_result", "snf_bgzf_read_stream"):
         getattr(lib, f).restype = C.c_int
