@@ -169,7 +169,14 @@ SNF_D void chain_scan(const View& v, int slot0, int64_t tile, const unsigned lon
 __global__ void __launch_bounds__(256) z0_init(const View v, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t T = v.T, G = 8 * T + 8;
-  if (i < (int64_t)(sizeof(Counts) / 8)) ((unsigned long long*)v.cnt)[i] = 0;
+  if (i < (int64_t)(sizeof(Counts) / 8)) {
+    // a resident window index (View::win_ready): its two totals are no longer written by a kernel of the pass - they go in here, with the
+    // reset of the word they live in, so that w6t_emit, the host and SNF_PROF find them in Counts as before
+    unsigned long long c0 = 0;
+    if (v.win_ready && i == (int64_t)(offsetof(Counts, n_valid) / 8)) c0 = (unsigned long long)v.win_n_valid;
+    if (v.win_ready && i == (int64_t)(offsetof(Counts, n_occ) / 8)) c0 = (unsigned long long)v.win_n_occ;
+    ((unsigned long long*)v.cnt)[i] = c0;
+  }
   if (i <= T) { v.t_cov_sum[i] = 0; v.t_status[i] = 0; }
   if (i <= T + 1) v.t_call_off[i] = 0;
   if (i < G) { v.grp_first_bin[i] = -1; v.grp_seed_lo[i] = -1; v.grp_seed_hi[i] = -1; v.grp_dirty[i] = 0; }

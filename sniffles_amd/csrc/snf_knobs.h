@@ -79,7 +79,8 @@ struct BatchKnobs {
   int f4_grid = env_pos("SNF_F4_GRID", 2048);         // SNF_F4_GRID=n (> 0), default 2048: grid cap of f4w_emit
   bool large_prio = env_on("SNF_LARGE_PRIO");        // SNF_LARGE_PRIO!=0: the third stream (SMALL consensus class) is created with the device's highest priority
   int readprep = env_int("SNF_READPREP", 1);         // SNF_READPREP=0..3, default 1: read preparation 0 first, 1 enqueued behind d1w (may start at once), 2 after d3_taskoff, 3 starts with d1w
-  bool readprep_each_pass = env_set("SNF_READPREP_EACH_PASS");   // SNF_READPREP_EACH_PASS (set): the read index rebuilt in every call_candidates (round-1 behaviour); no pass graph
+  bool readprep_each_pass = env_set("SNF_READPREP_EACH_PASS");   // SNF_READPREP_EACH_PASS (set): BOTH indexes built at upload - the read index and the window index (w1_hist .. w3_scatter) -
+                                                                 // are rebuilt in every call_candidates instead (the read index: round-1 behaviour); no pass graph
   // ---- where the result is stored (run_finalize)
   int stage_out = env_int("SNF_STAGE_OUT", -1);      // SNF_STAGE_OUT=0/1: result stored directly / staged through HBM; unset (< 0): staged while another pass is in flight
   bool stage_copy_kernel = env_is("SNF_STAGE_COPY", "kernel");   // SNF_STAGE_COPY=kernel: a staged result is copied by kernels inside the pass; default: two copies at the fetch

@@ -743,6 +743,7 @@ void stage_reads(const snf_task_input_t& t, uint8_t* st, const size_t* off, int6
 
 void enqueue_read_index(snf_batch_impl* b);
 void enqueue_pass_init(snf_batch_impl* b);
+void enqueue_window_index(snf_batch_impl* b, bool scatter);
 void join_open_candidates(snf_batch_impl* b);
 void enqueue_keys(snf_batch_impl* b);
 // coverage samples by the thread-per-call kernel d4_coverage instead of d4s_coverage (launch_coverage)
@@ -1003,7 +1004,7 @@ void do_upload(snf_batch_impl* b) {
     win_slots_max = win_layout(WIN_W_MIN, off);
     if (win_slots_max >= ((int64_t)1 << 31)) win_slots_max = 0;
   }
-  v.front = 0; v.NW = 0;
+  v.front = 0; v.NW = 0; v.win_ready = 0; v.win_stats = 0; v.win_n_valid = 0; v.win_n_occ = 0;
   if (win_slots_max > 0) {
     const size_t W1 = (size_t)win_slots_max + 1;
     v.wcnt = dalloc<uint32_t>(b, W1); v.wfill = dalloc<uint32_t>(b, W1); v.wbase = dalloc<uint32_t>(b, W1);
@@ -1099,32 +1100,41 @@ void do_upload(snf_batch_impl* b) {
   if (win_slots_max > 0 && v.NS > 0) {
     // window width: the widest whose largest window fits the 256-lead instance of the window kernels, else the widest that fits the
     // 1024-lead one; occupied windows and the largest window are properties of the input (counted here, like NS): the passes size
-    // their launches on the host
+    // their launches on the host.  The histogram and the scan that answer this for a width ARE the first half of the window index
+    // (enqueue_window_index): for the width that is accepted - the first one tried, in the usual case - they are kept and the scatter
+    // follows, once; the largest window and the windows of more than 64 leads come out of the scan (View::win_stats).
     int forced = b->k.win_bits;
-    int best_w = -1; int64_t best_occ = 0, best_max = 0, best_big = 0;
+    int best_w = -1; Counts best{};
     std::vector<int64_t> off;
     if (forced && (forced < WIN_W_MIN || forced > WIN_W_MAX)) forced = 0;
-    for (int W = forced ? forced : WIN_W_MAX; W >= (forced ? forced : WIN_W_MIN); W--) {
+    const bool tm = b->timing; b->timing = false;      // (no event brackets outside a pass)
+    auto count_windows = [&](int W) {
       v.NW = win_layout(W, off); v.win_bits = W;
-      const int64_t* d_off = upload_vec(b, off);
-      v.t_win_off = d_off;
-      const bool tm = b->timing; b->timing = false;
+      v.t_win_off = upload_vec(b, off);
       enqueue_pass_init(b);
-      LAUNCH_Q(w1_hist, v, N, 0);
-      LAUNCH_Q(w0_stats, v, v.NW, 0);
-      b->timing = tm;
+      v.win_stats = 1; enqueue_window_index(b, false); v.win_stats = 0;
       Counts hc{};
       d2h(b, &hc, v.cnt, sizeof(Counts));
-      dzero(b, v.wcnt, ((size_t)v.NW + 1) * 4);
-      dsync(b);
-      if (hc.max_win <= 256 || (best_w < 0 && hc.max_win <= SNF_WIN_MAXCAP)) { best_w = W; best_occ = hc.n_occ; best_max = hc.max_win; best_big = hc.n_big64; }
+      dsync(b);      // (also: `off` may be rewritten)
+      return hc;
+    };
+    for (int W = forced ? forced : WIN_W_MAX; W >= (forced ? forced : WIN_W_MIN); W--) {
+      const Counts hc = count_windows(W);
+      if (hc.max_win <= 256 || (best_w < 0 && hc.max_win <= SNF_WIN_MAXCAP)) { best_w = W; best = hc; }
       if (hc.max_win <= 256) break;
     }
+    if (best_w >= 0 && v.win_bits != best_w) best = count_windows(best_w);      // (rare: no width fits the 256-lead instance and a narrower one was tried last)
+    const int64_t best_occ = best.n_occ, best_max = best.max_win, best_big = best.n_big64;
     if (best_w >= 0) {
-      if (v.win_bits != best_w) { v.NW = win_layout(best_w, off); v.win_bits = best_w; v.t_win_off = upload_vec(b, off); dsync(b); }
+      LAUNCH_Q(w3_scatter, v, N, 0);
       v.front = 1; b->h_n_occ = best_occ; b->win_cap = best_max <= 64 ? 64 : best_max <= 256 ? 256 : SNF_WIN_MAXCAP;
+      v.win_n_valid = best.n_valid; v.win_n_occ = best_occ;
+      // the index stays: wbase, wlist, blk_k0 and the bucket array (key_in) are read-only from here on, and a pass starts at w4s_segment.
+      // SNF_READPREP_EACH_PASS: every pass builds it again, like the read index (enqueue_window_front)
+      v.win_ready = b->k.readprep_each_pass ? 0 : 1;
       b->h_n_big64 = best_big; v.w4_list = dalloc<int32_t>(b, (size_t)best_big + 64); v.w4_mode = 0;
     }
+    b->timing = tm;
     if (v.prof) fprintf(stderr, "[SNF_PROF] window front end: %s (W = %d: %lld windows, %lld occupied, largest %lld leads, %lld of more than 64: w4s_segment in %s)\n", v.front ? "on" : "off",
                         v.win_bits, (long long)v.NW, (long long)best_occ, (long long)best_max, (long long)best_big,
                         (b->k.w4_split && b->win_cap > 64 && best_big > 0 && best_big * 8 < (N + 63) / 64) ? "two launches" : "one launch");
@@ -1381,17 +1391,30 @@ void enqueue_keys(snf_batch_impl* b) {
   }
 }
 
-// the window front end (snf_stage_window.h): from the input leads to the seed table and the packed lead records in six launches
-void enqueue_window_front(snf_batch_impl* b) {
-  SNF_TRACE("A: window front end");
+// The window INDEX: every lead inside its contig in the bucket of its window (key_in), the buckets' offsets (wbase), the occupied windows
+// (wlist) and the first window of every 64 positions (blk_k0).  It is the device form of the LeadProvider's leadtab[svtype][bin] at window
+// granularity - LeadProvider.record_lead fills that table while the signatures are extracted (leadprov.py:400-418), before
+// Task.call_candidates - and a function of the lead table, cluster_binsize and W alone: built at upload, like the read index.
+// scatter = false: the histogram and the scan only (the upload, while it tries a width).
+void enqueue_window_index(snf_batch_impl* b, bool scatter) {
   View& v = b->v;
-  const int64_t N = v.N, NW = v.NW, n_occ = b->h_n_occ;
-  if (N <= 0 || n_occ <= 0) return;
-  Scope _all(b, "front_window", N * 21);
+  const int64_t N = v.N, NW = v.NW;
   LAUNCH_Q(w1_hist, v, N, 0);
   if (v.chain_on) CHAIN(w2c_offsets, NW);
   else { FUSED(w2a_sums, NW); FUSED(w2b_offsets, NW); }
-  LAUNCH_Q(w3_scatter, v, N, 0);
+  if (scatter) LAUNCH_Q(w3_scatter, v, N, 0);
+}
+
+// the window front end (snf_stage_window.h): from the window index to the seed table and the packed lead records in four launches
+// (w4s_segment, the w5 scan, w6t_emit); per-bin order, the 10-per-bin cap, the hap counters and seed eligibility are the pass's.
+// SNF_READPREP_EACH_PASS (View::win_ready == 0): the index is built here again, in front of them, as every pass did before.
+void enqueue_window_front(snf_batch_impl* b) {
+  SNF_TRACE("A: window front end");
+  View& v = b->v;
+  const int64_t N = v.N, n_occ = b->h_n_occ;
+  if (N <= 0 || n_occ <= 0) return;
+  Scope _all(b, "front_window", N * 21);
+  if (!v.win_ready) enqueue_window_index(b, true);
   const int64_t n_blk = (N + 63) / 64;      // waves of w4s_segment: one per 64 positions of the bucket array
   // SNF_W4_SPLIT=1: two launches when few blocks need more than the 64-lead instance (82 registers and 3.6 KB of LDS against 98 and 8.6 KB:
   // six waves per SIMD instead of four, two unrolled rounds instead of five): the small instance over every block, the large one over the
@@ -2203,8 +2226,8 @@ void do_fetch(snf_batch_impl* b, int stage, snf_result_t* out) {
   if (b->h_cnt->overflow) fail(b->h_cnt->overflow & 2 ? "internal: hand-over list of the call kernels overflowed" : "internal: fused-sequence pool overflow");
   if (v.prof) {
     const Counts& c = *b->h_cnt;
-    fprintf(stderr, "[SNF_PROF] counts: valid %lld bins %lld seeds %lld clusters %lld refined %lld calls %lld | cons calls %lld reads %lld "
-                    "fallback %lld alt bytes %lld fused bytes through the shared counter %llu (the rest in the waves' own slices; the split depends on scheduling, the total and the capacity do not) | ALT lists copy %llu small %llu large %llu/%llu/%llu/%llu thread %llu rows %llu\n", (long long)c.n_valid, (long long)c.n_bins, (long long)c.n_seeds, (long long)c.n_clusters,
+    fprintf(stderr, "[SNF_PROF] counts: valid %lld windows %lld bins %lld seeds %lld clusters %lld refined %lld calls %lld | cons calls %lld reads %lld "
+                    "fallback %lld alt bytes %lld fused bytes through the shared counter %llu (the rest in the waves' own slices; the split depends on scheduling, the total and the capacity do not) | ALT lists copy %llu small %llu large %llu/%llu/%llu/%llu thread %llu rows %llu\n", (long long)c.n_valid, (long long)c.n_occ, (long long)c.n_bins, (long long)c.n_seeds, (long long)c.n_clusters,
             (long long)c.n_rc, (long long)c.n_calls, (long long)c.n_cons, (long long)c.n_cons_reads, (long long)c.n_cons_fallback,
             (long long)c.alt_total, c.pool_extra_used, c.n_cls[0], c.n_cls[1], c.n_cls[2], c.n_cls[3], c.n_cls[4], c.n_cls[5], c.n_cls[6], c.n_cls[7]);
   }
@@ -2559,6 +2582,7 @@ void do_fetch_clusters(snf_batch_impl* b, int stage, snf_clusters_t* out) {
     const bool fin = b->finalized;
     full_sync(b);
     v.prefilter = 0; v.front = 0; v.NS = v.N;
+    v.win_ready = 0;      // (the sort path overwrites key_in / val_in: the window index is dead, and with `front` off nothing asks for it again)
     run_call_candidates(b);
     if (fin) run_finalize(b);
   }

@@ -2,6 +2,10 @@
 // sort of the lead keys and the seven binning launches behind it (a1_keys, a0k_*, rocPRIM onesweep = 16 launches, a2k ... a7k:
 // 26 launches, ~0.55 ms of a 1.9-ms pass) by six launches that never sort the whole table:
 //
+// The first three (four launches) build the window INDEX, a function of the lead table, cluster_binsize and W alone: they run at upload
+// and what they leave (wbase, wlist, blk_k0, the bucket array key_in, n_valid / n_occ) stays for the life of the handle.  A pass starts
+// at w4s_segment and writes none of it (View::win_ready; SNF_READPREP_EACH_PASS runs all of them in every pass).
+//
 //   w1_hist     per lead: (task, svtype, 100-bp bin) -> its WINDOW (2^W consecutive bins of one (task, svtype)); one count per window
 //   w2a / w2b   exclusive scan of the window counts (bucket offsets) + the list of occupied windows
 //   w3_scatter  per lead: into its window's bucket (any order inside a bucket)
@@ -72,25 +76,26 @@ __global__ void __launch_bounds__(256) w1_hist(const View v, int64_t n) {
   uint32_t w = ~0u, attr = 0;
   const bool valid = i < n && win_of_lead(v, i, &w, &attr);
   if (i < n) { v.val_in[i] = valid ? w : ~0u; v.val_out[i] = attr; }
-  if (i <= v.NS) v.rcflag[i] = 0;      // (reset for d1w_refine: rc_emit sets it; N >= NS)
   int cnt; bool leader;
   win_group(valid, w, &cnt, &leader);
   if (leader) atomicAdd(&v.wcnt[w], (uint32_t)cnt);
 }
 
-// W0 (upload only): occupied windows and the largest window of the batch
-__global__ void __launch_bounds__(256) w0_stats(const View v, int64_t n) {
-  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint32_t c = p < n ? v.wcnt[p] : 0u;
-  const unsigned long long occ = __ballot(c != 0);
+// (upload only, View::win_stats) the largest window of the batch and the windows of more than 64 leads, formed where the counts are scanned
+// anyway: one atomic per block that has something to report.  Counts::n_occ comes from the scan itself.
+SNF_D void win_stats(const View& v, uint32_t c) {
+  __shared__ uint32_t st_max[4], st_big[4];
   uint32_t m = c;
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) { const uint32_t y = (uint32_t)__shfl_xor((int)m, d, 64); if (y > m) m = y; }
   const unsigned long long big = __ballot(c > 64u);
-  if ((threadIdx.x & 63) == 0 && occ) {
-    atomicAdd((unsigned long long*)&v.cnt->n_occ, (unsigned long long)__popcll(occ));
-    atomicMax((unsigned long long*)&v.cnt->max_win, (unsigned long long)m);
-    if (big) atomicAdd((unsigned long long*)&v.cnt->n_big64, (unsigned long long)__popcll(big));
+  if ((threadIdx.x & 63) == 0) { st_max[threadIdx.x >> 6] = m; st_big[threadIdx.x >> 6] = (uint32_t)__popcll(big); }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t mm = st_max[0], nb = st_big[0];
+    for (int k = 1; k < 4; k++) { if (st_max[k] > mm) mm = st_max[k]; nb += st_big[k]; }
+    if (mm) atomicMax((unsigned long long*)&v.cnt->max_win, (unsigned long long)mm);
+    if (nb) atomicAdd((unsigned long long*)&v.cnt->n_big64, (unsigned long long)nb);
   }
 }
 
@@ -117,11 +122,12 @@ SNF_FUSED_HEAD(w2b_offsets)
   unsigned long long val[2] = {(unsigned long long)c, c ? 1ull : 0ull}, off[2];
   tile_scan<2>(v, TS_WIN, val, off, lds);
   if (p < n) {
-    v.wcnt[p] = 0; v.wfill[p] = 0;      // spent / not yet used in this pass: both counters are clean for w3_scatter and the next pass
+    v.wcnt[p] = 0; v.wfill[p] = 0;      // spent / not yet used by this build: both counters are clean for w3_scatter and the next build
     v.wbase[p] = (uint32_t)off[0];
     win_list(v, p, c, off[0], off[1]);
     if (p == n - 1) { v.wbase[n] = (uint32_t)(off[0] + val[0]); v.cnt->n_valid = (int64_t)(off[0] + val[0]); v.cnt->n_occ = (int64_t)(off[1] + val[1]); }
   }
+  if (v.win_stats) win_stats(v, c);
 }
 
 SNF_CHAIN_HEAD(w2c_offsets, TS_WIN)      // (the pair above in one launch: snf_fused.h chain_scan)
@@ -129,11 +135,12 @@ SNF_CHAIN_HEAD(w2c_offsets, TS_WIN)      // (the pair above in one launch: snf_f
   unsigned long long val[2] = {(unsigned long long)c, c ? 1ull : 0ull}, off[2], tot[2];
   chain_scan<2>(v, TS_WIN, tile, val, off, tot, lds);
   if (p < n) {
-    v.wcnt[p] = 0; v.wfill[p] = 0;      // spent / not yet used in this pass: both counters are clean for w3_scatter and the next pass
+    v.wcnt[p] = 0; v.wfill[p] = 0;      // spent / not yet used by this build: both counters are clean for w3_scatter and the next build
     v.wbase[p] = (uint32_t)off[0];
     win_list(v, p, c, off[0], off[1]);
     if (p == n - 1) { v.wbase[n] = (uint32_t)tot[0]; v.cnt->n_valid = (int64_t)tot[0]; v.cnt->n_occ = (int64_t)tot[1]; }
   }
+  if (v.win_stats) win_stats(v, c);
 }
 
 // W3: every lead into its window's bucket: (attributes << 32 | input index), any order inside the bucket
@@ -211,12 +218,13 @@ __global__ void __launch_bounds__(64) w4s_segment(const View v, int64_t n_unused
     i = v.w4_list[i];
   }
   const int64_t B0 = 64 * i;
-  const int64_t n_valid = v.cnt->n_valid;
+  // (a resident index: both totals are kernel arguments - no load in front of the first bucket words)
+  const int64_t n_valid = v.win_ready ? v.win_n_valid : v.cnt->n_valid;
   // the first 64 positions are this block's own: their words are requested before the wave knows which of them it owns
   uint64_t w0 = 0;
   if (B0 + lane < n_valid) w0 = v.key_in[B0 + lane];
   uint32_t k0 = 0, k1 = 0;
-  if (B0 < n_valid) { k0 = v.blk_k0[i]; k1 = B0 + 64 <= n_valid ? v.blk_k0[i + 1] : (uint32_t)v.cnt->n_occ; }
+  if (B0 < n_valid) { k0 = v.blk_k0[i]; k1 = B0 + 64 <= n_valid ? v.blk_k0[i + 1] : (uint32_t)(v.win_ready ? v.win_n_occ : v.cnt->n_occ); }
   const int nw = (int)(k1 - k0);                 // <= 64: every window holds a lead and starts inside the block
   if (nw <= 0) { if (lane == 0) { v.ws_seeds[i] = 0; v.ws_nf[i] = 0; v.ws_nl[i] = 0; } return; }
   uint4 wr = make_uint4(0, 0, 0, 0);             // {window, leads, bucket offset, task}
@@ -397,7 +405,8 @@ SNF_CHAIN_HEAD(w5c_offsets, TS_WINC)     // (the pair above in one launch)
 __global__ void __launch_bounds__(256) w6t_emit(const View v, int64_t n_unused) {
   IT_SCOPE(3)
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= v.cnt->n_valid) return;
+  if (p <= v.NS) v.rcflag[p] = 0;      // (reset for d1w_refine: rc_emit sets it; the grid covers the N >= NS input leads)
+  if (p >= (v.win_ready ? v.win_n_valid : v.cnt->n_valid)) return;
   const uint64_t word = v.key_out[p];
   const uint32_t hi = (uint32_t)(word >> 32), o = (uint32_t)word;
   if (!(hi & (SNF_WS_NORM | SNF_WS_LONG))) return;      // (a seed lead is one of the two)

@@ -20,7 +20,7 @@ struct Counts {
   int64_t n_kept;            // leads the occupancy prefilter lets through to the sort (a0_*; == NS whenever the prefilter is on)
   int64_t n_big[3];          // items the wave kernels handed to x_big<0 / 1 / 2> in this pass (sums of View::big_cnt, formed by z1_results)
   int64_t n_occ;             // window front end (snf_stage_window.h): occupied windows of this pass
-  int64_t max_win;           // ... and the largest window (only formed at upload, w0_stats)
+  int64_t max_win;           // ... and the largest window (only formed at upload: w2 with View::win_stats)
   int64_t n_big64;           // ... and the windows of more than 64 leads (upload): at most that many blocks need the large instance of w4s_segment
   unsigned long long n_w4big;       // blocks the small instance of w4s_segment handed on in this pass (View::w4_list)
   int64_t n_cons_fallback;   // consensus calls that do not fit the LDS workgroup kernel
@@ -198,7 +198,13 @@ struct View {
   int32_t win_bits;           // W
   int64_t NW;                 // window slots of the batch (dense: per task SNF_NTYPES x windows of its contig)
   const int64_t* t_win_off;   // [T+1] first window of task t
-  uint32_t *wcnt, *wfill;     // [NW+1] leads per window / fill cursor of the scatter (both zero between passes)
+  // The INDEX half (w1_hist .. w3_scatter: wbase, wlist, blk_k0 and the bucket array key_in) depends on the lead table, cluster_binsize
+  // and W alone: built once at upload and resident for the life of the handle.  A pass then starts at w4s_segment and writes none of it.
+  int32_t win_ready;          // 1: the index is resident (0: SNF_READPREP_EACH_PASS rebuilds it in every pass; always 0 once `front` is off)
+  int32_t win_stats;          // 1 (upload only): the scan of the window counts also forms Counts::max_win / n_big64
+  int64_t win_n_valid, win_n_occ;   // leads inside their contig / occupied windows, as the upload's scan counted them: with a resident index
+                                    // z0_init stores both into Counts at the start of every pass, and the window kernels read them from here
+  uint32_t *wcnt, *wfill;     // [NW+1] leads per window / fill cursor of the scatter (wcnt is zero between builds of the index; w2 clears both)
   uint32_t* wbase;            // [NW+1] bucket offsets (exclusive scan of wcnt)
   uint32_t* wlist;            // [4 x n_occ] occupied windows, ascending: {window, leads, bucket offset, task}
   uint32_t* blk_k0;           // [N / 64 + 2] per 64 positions of the bucket array: the first occupied window starting there or behind
