@@ -35,7 +35,6 @@ struct BatchKnobs {
                                                      //   also: no window front end, no deferred read names
   bool sort64 = env_set("SNF_SORT64");               // SNF_SORT64 (set): tests - force the wide-key sorts; default: 32-bit keys where they fit
   bool prefilter = !env_set("SNF_NO_PREFILTER");     // SNF_NO_PREFILTER (set): every lead through the sort; default: the occupancy prefilter
-  bool pf_spread = env_int("SNF_PF_SPREAD", 0) == 1; // SNF_PF_SPREAD=1: bitmap cells spread over L2 channels (measured: a1_keys 0.146 ms spread / 0.111 adjacent)
   bool winfront = !env_set("SNF_NO_WINFRONT");       // SNF_NO_WINFRONT (set): the sort path instead of the window front end (snf_stage_window.h)
   int win_bits = env_int("SNF_WIN_BITS", 0);         // SNF_WIN_BITS=k: window width forced to 2^k bins (6..win_bits_max; 0 / out of range: chosen from the data)
   int win_bits_max = [] { const int v = env_int("SNF_WIN_BITS_MAX", 10); return v >= 6 && v <= 12 ? v : 10; }();   // SNF_WIN_BITS_MAX=6..12, default 10 (anything
@@ -64,27 +63,16 @@ struct BatchKnobs {
   bool rn_defer = !env_set("SNF_NO_RN_DEFER");       // SNF_NO_RN_DEFER (set): all read names in the candidate stage; default (SNF_OUT_EXECUTE): only for the calls that pass QC
   bool rn_fuse = !env_set("SNF_NO_RN_FUSE");         // SNF_NO_RN_FUSE (set): read names of the kept calls by a pass of their own; default: written by f4w_emit
   // ---- grids, occupancy, scheduling inside a pass (experiments)
-  int grid_mult = env_int("SNF_GRID_MULT", 2);       // SNF_GRID_MULT=k, default 2: resident sets the grid-stride wave kernels are launched with
-  int grid_div = env_pos("SNF_GRID_DIV", 1);         // SNF_GRID_DIV=k (> 0), default 1: a fraction of the resident set (room for the other pass in flight)
-  int occ_d2 = env_int("SNF_OCC_D2", 5);             // SNF_OCC_D2, default 5: waves/SIMD d2w_call is compiled for; <6> and <8> spill (36 / 100 B of scratch); <5> does not and is as fast
-  int occ_e1 = env_int("SNF_OCC_E1", 5);             // SNF_OCC_E1=4/5/6, default 5: ... e1w_finalize (<8> trips a register-allocation bug of this hipcc)
-  int occ_s = env_int("SNF_OCC_S", 5);               // SNF_OCC_S=5/6/8, default 5: ... the four-wave SMALL consensus kernel
   int cons_nw = env_int("SNF_CONS_NW", 1);           // SNF_CONS_NW=1/4: waves per SMALL consensus call; 1 (default): single-wave workgroups leave room for the LARGE class next
                                                      //   to them - LARGE in place 0.75 -> 0.5 ms, the pass 2.5 % shorter
   int cons_large_nw = env_int("SNF_CONS_LARGE_NW", 4); // SNF_CONS_LARGE_NW=4/8/16, default 4: waves per LARGE consensus call
-  int cons_grid_mult = env_int("SNF_CONS_GRID_MULT", KNOB_UNSET); // SNF_CONS_GRID_MULT=k: consensus grids capped at k x the resident workgroups (the kernels stride); unset: plain grids
-  int cons_small_grid = env_pos("SNF_CONS_SMALL_GRID", 65536); // SNF_CONS_SMALL_GRID=n (> 0), default 65536: the one-wave SMALL kernel strides beyond this many workgroups
   int cons_order = env_int("SNF_CONS_ORDER", -1);    // SNF_CONS_ORDER=0/1/2: order of the consensus classes (enqueue_consensus_wave); unset (< 0): 2 with another pass in flight, else 0
   bool serial = env_set("SNF_SERIAL");               // SNF_SERIAL (set): dev - every ALT kernel alone on the device (isolated timings); no pass graph
-  int f4_grid = env_pos("SNF_F4_GRID", 2048);         // SNF_F4_GRID=n (> 0), default 2048: grid cap of f4w_emit
-  bool large_prio = env_on("SNF_LARGE_PRIO");        // SNF_LARGE_PRIO!=0: the third stream (SMALL consensus class) is created with the device's highest priority
-  int readprep = env_int("SNF_READPREP", 1);         // SNF_READPREP=0..3, default 1: read preparation 0 first, 1 enqueued behind d1w (may start at once), 2 after d3_taskoff, 3 starts with d1w
   bool readprep_each_pass = env_set("SNF_READPREP_EACH_PASS");   // SNF_READPREP_EACH_PASS (set): BOTH indexes built at upload - the read index and the window index (w1_hist .. w3_scatter) -
                                                                  // are rebuilt in every call_candidates instead (the read index: round-1 behaviour); no pass graph
   // ---- where the result is stored (run_finalize)
   int stage_out = env_int("SNF_STAGE_OUT", -1);      // SNF_STAGE_OUT=0/1: result stored directly / staged through HBM; unset (< 0): staged while another pass is in flight
   bool stage_copy_kernel = env_is("SNF_STAGE_COPY", "kernel");   // SNF_STAGE_COPY=kernel: a staged result is copied by kernels inside the pass; default: two copies at the fetch
-  bool alt_hbm = env_set("SNF_ALT_HBM");             // SNF_ALT_HBM (set): measurement - only the ALT bytes into HBM, copied at fetch
   // ---- timing and reports (b->timing / time_every / time_all start from these and change through snf_batch_set_timing / snf_batch_timing_every)
   bool prof = env_set("SNF_PROF");                   // SNF_PROF (set): [SNF_PROF] lines to stderr - stage counters, the forms a handle launches, the upload's split
   bool timing = !env_set("SNF_NO_TIMING");           // SNF_NO_TIMING (set): no HIP events around the kernels
@@ -97,7 +85,6 @@ struct BatchKnobs {
 struct ProcessKnobs {
   int pace = env_int("SNF_PACE", 1);                 // SNF_PACE=0/1/2/3, default 1: the rules that keep passes in flight out of step - 0 off, 1 both, 2 copies in turn only, 3 spaced starts only
   double pace_frac = getenv("SNF_PACE_FRAC") ? atof(getenv("SNF_PACE_FRAC")) : 0.25;   // SNF_PACE_FRAC=f, default 0.25: spacing of pass starts as a fraction of the recent pass latency
-  bool chain_gate = env_on("SNF_CHAIN_GATE");        // SNF_CHAIN_GATE!=0: the passes of a device take turns with their chains through a device-side event (measured, not the default)
   int gpu_slots = env_int("SNF_GPU_SLOTS", 0);       // SNF_GPU_SLOTS=n, default 0 (unbounded): at most n passes - of any process of this user - drive a device at a time
   size_t stage_arena_floor = getenv("SNF_STAGE_ARENA_MB") ? (size_t)atoll(getenv("SNF_STAGE_ARENA_MB")) << 20 : 0;   // SNF_STAGE_ARENA_MB=n: the pinned staging arena is never smaller (server.py)
   bool slab_cache = !env_set("SNF_NO_SLAB_CACHE");   // SNF_NO_SLAB_CACHE (set): no device-slab cache - every batch allocates and frees its own slabs

@@ -266,9 +266,9 @@ struct snf_batch_impl {
   int device = 0;
   hipStream_t stream = nullptr;   // main stream (also the one fetch/sync wait on)
   hipStream_t stream2 = nullptr;  // side stream: read preparation, finalize scalar kernels
-  hipStream_t stream3 = nullptr;  // third stream: the SMALL consensus class and the verbatim copies next to the LARGE class (k.large_prio: highest priority)
+  hipStream_t stream3 = nullptr;  // third stream: the SMALL consensus class and the verbatim copies next to the LARGE class
   hipStream_t stream4 = nullptr;  // fourth stream: sv ids + supporting read names and their D2H copy (off the coverage / QC chain)
-  hipStream_t cur = nullptr;      // stream the LAUNCH / prim_* helpers enqueue on
+  hipStream_t cur = nullptr;      // stream the KERNEL_* / prim_* helpers enqueue on
   int cur_slot = 0;
   bool fused = false;             // flag -> scan -> emit chains as fused kernel pairs (snf_fused.h); off (k.fuse off, or > 2^25 leads; set at upload): rocPRIM scans
   bool timing = true;             // HIP events around the heavy kernels (snf_batch_set_timing)
@@ -278,9 +278,7 @@ struct snf_batch_impl {
   uint64_t pass_count = 0;        //   1.29-ms step with two batches in flight when every pass carried them
   bool res_current = false;       // z1_results has run after the last kernel that changes what it publishes
   int64_t* h_rn_total = nullptr;  // pinned (hb_res): see View::res_rn_total
-  void (*k_d2w)(const View, int64_t) = nullptr; void (*k_e1w)(const View, int64_t) = nullptr;  // occupancy variants
   int slots_d1w = 8192, slots_d2w = 8192, slots_e1w = 8192, slots_big = 8192;
-  int slots_cons_s = 1 << 22, slots_cons_l = 1 << 22, slots_cons_s1 = 65536;   // grid caps of the SMALL / LARGE consensus kernels
   int read_key_bits = 64;         // significant bits of the read-end sort key
   std::vector<int32_t> h_rend_max; // per task: largest read end (filled by the upload's validation pass)
   bool uploaded = false;
@@ -299,7 +297,6 @@ struct snf_batch_impl {
   int slot_fd = -1;               // the GPU slot this pass holds (SNF_GPU_SLOTS)
   double pass_start_ms = 0.0;     // when this handle's pass in flight began (pacing of overlapping passes)
   bool capturing = false;         // run_pass is capturing this pass into a graph
-  int chain_slot = -1;            // SNF_CHAIN_GATE: the device's event this pass records at the end of its chain
   // Result staged through HBM (run_finalize): with another pass in flight on the device the kernels of a pass store the result block
   // and the ALT section into HBM; they are taken to the pinned buffers by two copies at the fetch (default) or by two small copy
   // kernels behind their producers (SNF_STAGE_COPY=kernel: z2_stage_copy reads the sizes on the device)
@@ -487,12 +484,19 @@ T* upload_vec(snf_batch_impl* b, const std::vector<T>& h, size_t extra = 0) {
 }
 
 // ---- timing ----
+// When an operation is bracketed by a pair of timing events (two event records cost more host time than a launch, and keep the
+// stream from running launches back to back):
+enum class Bracket {
+  heavy,    // on the handle's sampled passes (begin_pass_timing): the kernels a step's time is made of
+  quiet,    // only under SNF_TIME_ALL: the tiny kernels of the launch-bound regions (stages A-C, the scans' halves)
+  always,   // on every pass: the kernel bench.py states the roofline on (LARGE consensus and nothing else)
+  none      // never: a launch inside a Scope of the caller's that spans several launches (the two of a split w4s_segment)
+};
 struct Scope {
   snf_batch_impl* b;
   size_t idx = (size_t)-1;
-  // always: bracketed on every pass (the kernel bench.py states the roofline on); the others only on the handle's sampled passes
-  Scope(snf_batch_impl* b_, const char* name, int64_t bytes, bool always = false) : b(b_) {
-    if (!b->timing || !(always || b->time_now)) return;
+  Scope(snf_batch_impl* b_, const char* name, int64_t bytes, Bracket br = Bracket::heavy) : b(b_) {
+    if (!b->timing || br == Bracket::none || (br == Bracket::quiet && !b->time_all) || !(br == Bracket::always || b->time_now)) return;
     if (b->ev_used == b->evs.size()) {
       snf_batch_impl::Ev e{};
       SNF_HIP(hipEventCreate(&e.a)); SNF_HIP(hipEventCreate(&e.b));
@@ -509,46 +513,26 @@ struct Scope {
 
 void d2h_timed(snf_batch_impl* b, void* dst, const void* src, size_t bytes, const char* name) {
   if (!bytes) return;
-  if (b->time_all) { Scope _s(b, name, (int64_t)bytes); d2h(b, dst, src, bytes); }
-  else d2h(b, dst, src, bytes);
+  Scope _s(b, name, (int64_t)bytes, Bracket::quiet);
+  d2h(b, dst, src, bytes);
 }
 
-// LAUNCH_Q: tiny kernels are only bracketed by events when SNF_TIME_ALL=1 (two event records cost more host time
-// than the launch itself and the stage A-C region is launch-bound)
-#define LAUNCH_Q(kern, view, n, bytes)                                                        \
+// ---- the launches of the batch code: on b->cur, bracketed under a timing name by one of the policies above, the view by value (a
+// caller that launches with a field of b->v changed writes it, launches and restores it).  They are macros because hipLaunchKernelGGL
+// is one and has to see the kernel as it is written: the runtime of the GPU-less test tier takes a kernel's name from that text.
+// KERNEL_GRID: a fixed grid; `arg` is the kernel's second parameter (0 where it has no use for one)
+#define KERNEL_GRID(kern, grid, block, view, arg, name, bytes, br)                            \
   do {                                                                                        \
-    int64_t _n = (n);                                                                         \
-    if (_n > 0) {                                                                             \
-      if (b->time_all) { Scope _s(b, #kern, (bytes));                                         \
-        hipLaunchKernelGGL(kern, dim3((unsigned)((_n + 255) / 256)), dim3(256), 0, b->cur, view, _n); } \
-      else hipLaunchKernelGGL(kern, dim3((unsigned)((_n + 255) / 256)), dim3(256), 0, b->cur, view, _n); \
-      SNF_HIP(hipGetLastError());                                                             \
-    }                                                                                         \
+    Scope _s(b, name, (bytes), Bracket::br);                                                  \
+    hipLaunchKernelGGL(kern, grid, block, 0, b->cur, view, (int64_t)(arg));                   \
+    SNF_HIP(hipGetLastError());                                                               \
   } while (0)
-#define LAUNCH(kern, view, n, bytes)                                                          \
+// KERNEL_N: n elements, 256 per block, n handed to the kernel, the timing name the kernel's; nothing for n <= 0
+#define KERNEL_N(kern, view, n, bytes, br)                                                    \
   do {                                                                                        \
-    int64_t _n = (n);                                                                         \
-    if (_n > 0) {                                                                             \
-      Scope _s(b, #kern, (bytes));                                                            \
-      hipLaunchKernelGGL(kern, dim3((unsigned)((_n + 255) / 256)), dim3(256), 0, b->cur, view, _n); \
-      SNF_HIP(hipGetLastError());                                                             \
-    }                                                                                         \
+    const int64_t _n = (n);                                                                   \
+    if (_n > 0) KERNEL_GRID(kern, dim3((unsigned)((_n + 255) / 256)), dim3(256), view, _n, #kern, bytes, br); \
   } while (0)
-
-// kernels of snf_fused.h: n elements, 256 per block; bracketed by timing events only with SNF_TIME_ALL
-#define FUSED(kern, n)                                                                                  \
-  do {                                                                                                  \
-    int64_t _n = (n);                                                                                   \
-    if (_n > 0) {                                                                                       \
-      if (b->time_all) { Scope _s(b, #kern, 0);                                                         \
-        hipLaunchKernelGGL(kern, dim3((unsigned)((_n + 255) / 256)), dim3(256), 0, b->cur, v, _n); }    \
-      else hipLaunchKernelGGL(kern, dim3((unsigned)((_n + 255) / 256)), dim3(256), 0, b->cur, v, _n);   \
-      SNF_HIP(hipGetLastError());                                                                       \
-    }                                                                                                   \
-  } while (0)
-
-// single-launch scan chains (snf_fused.h chain_scan)
-#define CHAIN(kern, n) FUSED(kern, n)
 
 // ---- primitives: stable radix sort (key,value) and exclusive scans ----
 template <class K>
@@ -901,7 +885,7 @@ void do_upload(snf_batch_impl* b) {
       d2d(b, d_in + off[IC_REND] + (size_t)r0 * 4, q.read_end, (size_t)q.n_reads * 4);
       d2d(b, d_in + off[IC_RHP] + (size_t)r0, q.read_hp, (size_t)q.n_reads);
       RebaseView rv{(int64_t*)(d_in + off[IC_SEQ_OFF]) + l0, (const int32_t*)(d_in + off[IC_SEQ_LEN]) + l0, p0};
-      LAUNCH_Q(u0_rebase, rv, q.n_leads, q.n_leads * 12);
+      KERNEL_N(u0_rebase, rv, q.n_leads, q.n_leads * 12, quiet);
     }
     // top level of the read-start index (every 256th start): from the staging arena, or back from HBM when some of the
     // starts never were on the host
@@ -942,8 +926,8 @@ void do_upload(snf_batch_impl* b) {
     q.first = v.in_first; q.rev = v.in_rev;
     LeadRec* rec = dalloc<LeadRec>(b, (size_t)N); int32_t* lt = dalloc<int32_t>(b, (size_t)N); int32_t* rt = dalloc<int32_t>(b, (size_t)R);
     q.rec = rec; q.lead_task = lt; q.r_task = rt;
-    LAUNCH_Q(u1_pack, q, N, N * 136);
-    LAUNCH_Q(u2_readtask, q, R, R * 4);
+    KERNEL_N(u1_pack, q, N, N * 136, quiet);
+    KERNEL_N(u2_readtask, q, R, R * 4, quiet);
     v.in_rec = rec; v.lead_task = lt; v.r_task = rt;
   }
   v.rk_in = dalloc<uint64_t>(b, R); v.rk_out = dalloc<uint64_t>(b, R); v.rv_in = dalloc<uint32_t>(b, R); v.rv_out = dalloc<uint32_t>(b, R);
@@ -980,8 +964,7 @@ void do_upload(snf_batch_impl* b) {
     if (N > 0 && b->cfg.dev_min_leads_cluster >= 2 && b->k.prefilter && cells < ((int64_t)1 << 36)) {
       v.prefilter = 1;
       v.t_cell_off = upload_vec(b, cell_off);
-      b->pf_words = (((cells >> 19) + 1) << 19) / 16 + 2;   // (whole 2^19-cell blocks: pf_slot permutes inside a block)
-      v.pf_spread = b->k.pf_spread ? 1 : 0;
+      b->pf_words = (((cells >> 19) + 1) << 19) / 16 + 2;   // (whole 2^19-cell blocks)
       v.pf_bm = dalloc<uint32_t>(b, (size_t)b->pf_words);
       dzero(b, v.pf_bm, (size_t)b->pf_words * 4);
       v.pf_key = dalloc<uint64_t>(b, N); v.pf_keep = dalloc<uint32_t>(b, N1); v.pf_scan = dalloc<uint32_t>(b, N1);
@@ -1126,7 +1109,7 @@ void do_upload(snf_batch_impl* b) {
     if (best_w >= 0 && v.win_bits != best_w) best = count_windows(best_w);      // (rare: no width fits the 256-lead instance and a narrower one was tried last)
     const int64_t best_occ = best.n_occ, best_max = best.max_win, best_big = best.n_big64;
     if (best_w >= 0) {
-      LAUNCH_Q(w3_scatter, v, N, 0);
+      KERNEL_N(w3_scatter, v, N, 0, quiet);
       v.front = 1; b->h_n_occ = best_occ; b->win_cap = best_max <= 64 ? 64 : best_max <= 256 ? 256 : SNF_WIN_MAXCAP;
       v.win_n_valid = best.n_valid; v.win_n_occ = best_occ;
       // the index stays: wbase, wlist, blk_k0 and the bucket array (key_in) are read-only from here on, and a pass starts at w4s_segment.
@@ -1164,7 +1147,7 @@ void do_upload(snf_batch_impl* b) {
     if (any_deep && R > 0) {
       MaxDepth md{v.r_start, v.re_sorted, v.rs_top, v.re_top, v.r_task, v.t_read_off, b->d_max_depth};
       const bool tm = b->timing; b->timing = false;
-      LAUNCH_Q(r3_maxdepth, md, R, R * 8);
+      KERNEL_N(r3_maxdepth, md, R, R * 8, quiet);
       b->timing = tm;
       d2h(b, maxd.data(), b->d_max_depth, sizeof(int32_t) * (size_t)T);
       dsync(b);
@@ -1201,10 +1184,6 @@ struct DevicePacing {
   std::atomic<long long> last_overlap_ms{-1000000};      // when two passes were last in flight together (now_ms clock)
   std::mutex copy_mu, pace_mu;
   double last_pass_start_ms = -1e12, pass_latency_ms = 0.0;      // (under pace_mu) start of the latest pass; smoothed enqueue -> waited time
-  // the chain gate (SNF_CHAIN_GATE=1; under pace_mu): the passes of a device take turns with their clustering / calling chains ON THE DEVICE - a pass's
-  // main stream waits for the event the pass before it recorded where its chain ends (in front of its ALT stage), while that pass's ALT
-  // and output stages run beside the new chain
-  hipEvent_t chain_ev[2] = {nullptr, nullptr}; unsigned long long chain_seq = 0;
 };
 DevicePacing g_pacing[SNF_MAX_DEVICES];
 DevicePacing& pacing_of(const snf_batch_impl* b) { return g_pacing[(b->device >= 0 && b->device < SNF_MAX_DEVICES) ? b->device : 0]; }
@@ -1216,11 +1195,7 @@ DevicePacing& pacing_of(const snf_batch_impl* b) { return g_pacing[(b->device >=
 // shared anyway; the pass that waited starts its next pass later - a stagger), (2) a pass does not START sooner than a quarter of the
 // recent pass latency after the other in-flight pass did (the second of two simultaneous starts waits ~0.4 ms once; passes that are
 // half a period apart never wait).  SNF_PACE=0 turns both off (2: rule 1 only, 3: rule 2 only), SNF_PACE_FRAC sets the fraction.
-// SNF_CHAIN_GATE=1 (off by default): passes of one device take turns with their chains ON THE DEVICE instead of being kept apart by the two
-// timing rules below.  Measured on the last day of round 6 (tools/regime.sh, profiles/r06_regime*.log): 8 of 8 and 8 of 8 runs at 0.954-0.977
-// ms per step (with rule 1) / 0.959-0.961 (without any rule) on one box - and, made the default, 12 of 16 runs at 0.955-0.97 but FOUR at
-// 1.32-1.49 (the passes one after the other) on the next.  The rules: 37 of 40 default runs of that day at 0.94-0.97, three at 1.15-1.19.
-// Not understood in the time left; the rules stay the default.
+// (A device-side gate between the chains of two passes was measured in their place and retired: DESIGN.md, "Retired switches".)
 bool pace_on() { return process_knobs().pace == 1 || process_knobs().pace == 3; }          // SNF_PACE: 0 off, 1 both rules, 2 copies in turn only, 3 spaced starts only
 bool pace_copy_turn() { return process_knobs().pace == 1 || process_knobs().pace == 2; }
 // GPU slots (SNF_GPU_SLOTS=n, off by default): at most n passes - of any process of this user - drive a device at a time.  The
@@ -1254,7 +1229,7 @@ void pass_begins(snf_batch_impl* b) {
   DevicePacing& P = pacing_of(b);
   const bool other = P.passes_in_flight.fetch_add(1) >= 1;
   if (other) P.last_overlap_ms.store((long long)now_ms());
-  if (!pace_on() || process_knobs().chain_gate) { b->pass_start_ms = now_ms(); return; }
+  if (!pace_on()) { b->pass_start_ms = now_ms(); return; }
   double wait = 0.0;
   {
     std::lock_guard<std::mutex> g(P.pace_mu);
@@ -1303,10 +1278,10 @@ void enqueue_read_index(snf_batch_impl* b) {
   View& v = b->v;
   const int64_t R = v.R;
   if (R <= 0) return;
-  LAUNCH(r1_endkeys, b->rp, R, R * 13);
+  KERNEL_N(r1_endkeys, b->rp, R, R * 13, heavy);
   if (b->rp.key32) prim_sort_pairs<uint32_t>(b, (uint32_t*)v.rk_in, (uint32_t*)v.rk_out, v.rv_in, v.rv_out, R, b->read_key_bits, "sort_read_ends");
   else prim_sort_pairs<uint64_t>(b, v.rk_in, v.rk_out, v.rv_in, v.rv_out, R, b->read_key_bits, "sort_read_ends");
-  LAUNCH_Q(r2_unpack, b->rp, R, R * 16);
+  KERNEL_N(r2_unpack, b->rp, R, R * 16, quiet);
   // haplotype prefix counts: HP 1 and HP 2 packed in one 64-bit scan per order (HP 0 = rank - both)
   prim_exscan<uint64_t>(b, b->rp.fs2, v.pc_s2, R + 1, "scan_hap_prefix");
   prim_exscan<uint64_t>(b, b->rp.fe2, v.pc_e2, R + 1, "scan_hap_prefix");
@@ -1322,6 +1297,7 @@ void enqueue_read_prep(snf_batch_impl* b) {
   if (R > 0) {
     if (b->k.readprep_each_pass) enqueue_read_index(b);
     // Task.coverage_average_total = coverage.mean(): sum of the clipped read lengths (exact) / contig length
+    // (this launch is spelt out, not KERNEL_GRID: tests/size_classes.py reads the chunk of d5w_covsum from the two lines as they stand)
     { Scope _s(b, "d5w_covsum", R * 12);
       int64_t grid = (R + 4095) / 4096; if (grid > 2048) grid = 2048;
       hipLaunchKernelGGL(d5w_covsum, dim3((unsigned)grid), dim3(256), 0, b->cur, v, (int64_t)0);
@@ -1334,9 +1310,9 @@ void enqueue_read_prep(snf_batch_impl* b) {
       p.q.lo = b->h_read_off[(size_t)t]; p.q.hi = b->h_read_off[(size_t)t + 1]; p.q.L = b->tasks[(size_t)t].contig_len;
       p.q.nm_start = v.nm_start; p.q.nm_end = v.nm_end; p.q.nm_lo = b->h_nm_off[(size_t)t]; p.q.nm_hi = b->h_nm_off[(size_t)t + 1];
       p.out = v.t_cov_sum + t;
-      LAUNCH_Q(d5x_covexact, p, (p.q.L + SNF_COVX_CHUNK - 1) / SNF_COVX_CHUNK, 0);
+      KERNEL_N(d5x_covexact, p, (p.q.L + SNF_COVX_CHUNK - 1) / SNF_COVX_CHUNK, 0, quiet);
     }
-  LAUNCH_Q(d5_covavg, v, T, 0);
+  KERNEL_N(d5_covavg, v, T, 0, quiet);
   }
 }
 
@@ -1344,11 +1320,9 @@ void enqueue_read_prep(snf_batch_impl* b) {
 // (d4s_coverage, snf_wave_call.h); SNF_D4=thread: the former thread-per-call kernel with its hinted binary searches
 void launch_coverage(snf_batch_impl* b, int64_t N) {
   View& v = b->v;
-  if (coverage_per_call(b)) { LAUNCH(d4_coverage, v, N, 0); return; }
-  Scope _s(b, "d4_coverage", 0);
+  if (coverage_per_call(b)) { KERNEL_N(d4_coverage, v, N, 0, heavy); return; }
   int64_t grid = (5 * N + 255) / 256; if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(d4s_coverage, dim3((unsigned)grid), dim3(256), 0, b->cur, v, (int64_t)0);
-  SNF_HIP(hipGetLastError());
+  KERNEL_GRID(d4s_coverage, dim3((unsigned)grid), dim3(256), v, 0, "d4_coverage", 0, heavy);
 }
 
 // start of a pass: every small reset (one launch on the fused path)
@@ -1361,7 +1335,7 @@ void enqueue_pass_init(snf_batch_impl* b) {
     if ((int64_t)(sizeof(Counts) / 8) > n0) n0 = (int64_t)(sizeof(Counts) / 8);
     if (3 * 64 * 16 > n0) n0 = 3 * 64 * 16;
     if (v.tile_stride > n0) n0 = v.tile_stride;
-    FUSED(z0_init, n0);
+    KERNEL_N(z0_init, v, n0, 0, quiet);
   } else {
     dzero(b, v.cnt, sizeof(Counts));
     dzero(b, v.t_cov_sum, sizeof(unsigned long long) * (T + 1));
@@ -1379,15 +1353,15 @@ void enqueue_keys(snf_batch_impl* b) {
   View& v = b->v;
   const int64_t N = v.N;
   if (N <= 0) return;
-  LAUNCH(a1_keys, v, N, N * 21);
+  KERNEL_N(a1_keys, v, N, N * 21, heavy);
   if (!v.prefilter) return;
   if (b->fused) {
-    { Scope _s(b, "a0_keep", N * 8); FUSED(a0k_keep, N); }
-    FUSED(a0k_compact, N);
+    { Scope _s(b, "a0_keep", N * 8); KERNEL_N(a0k_keep, v, N, 0, quiet); }
+    KERNEL_N(a0k_compact, v, N, 0, quiet);
   } else {
-    LAUNCH(a0_keep, v, N, N * 8);
+    KERNEL_N(a0_keep, v, N, N * 8, heavy);
     prim_exscan<uint32_t>(b, v.pf_keep, v.pf_scan, N + 1, "scan_keep");
-    LAUNCH_Q(a0_compact, v, N, N * 12);
+    KERNEL_N(a0_compact, v, N, N * 12, quiet);
   }
 }
 
@@ -1399,10 +1373,10 @@ void enqueue_keys(snf_batch_impl* b) {
 void enqueue_window_index(snf_batch_impl* b, bool scatter) {
   View& v = b->v;
   const int64_t N = v.N, NW = v.NW;
-  LAUNCH_Q(w1_hist, v, N, 0);
-  if (v.chain_on) CHAIN(w2c_offsets, NW);
-  else { FUSED(w2a_sums, NW); FUSED(w2b_offsets, NW); }
-  if (scatter) LAUNCH_Q(w3_scatter, v, N, 0);
+  KERNEL_N(w1_hist, v, N, 0, quiet);
+  if (v.chain_on) KERNEL_N(w2c_offsets, v, NW, 0, quiet);
+  else { KERNEL_N(w2a_sums, v, NW, 0, quiet); KERNEL_N(w2b_offsets, v, NW, 0, quiet); }
+  if (scatter) KERNEL_N(w3_scatter, v, N, 0, quiet);
 }
 
 // the window front end (snf_stage_window.h): from the window index to the seed table and the packed lead records in four launches
@@ -1424,24 +1398,23 @@ void enqueue_window_front(snf_batch_impl* b) {
   // 0.917-0.939 ms with two passes in flight, 1.344-1.351 against 1.325-1.344 with one.  Not the default.
   const bool split = b->k.w4_split && b->win_cap > 64 && b->h_n_big64 > 0 && b->h_n_big64 * 8 < n_blk;
   {
-    Scope* sc = b->time_all ? new Scope(b, "w4s_segment", 0) : nullptr;
+    Scope _w4(b, "w4s_segment", 0, Bracket::quiet);      // (one bracket over both launches of the split form)
+    const dim3 all((unsigned)n_blk), big((unsigned)b->h_n_big64);
     if (split) {
       v.w4_mode = 1;
-      hipLaunchKernelGGL(w4s_segment<64>, dim3((unsigned)n_blk), dim3(64), 0, b->cur, v, (int64_t)0);
+      KERNEL_GRID(w4s_segment<64>, all, dim3(64), v, 0, "w4s_segment", 0, none);
       v.w4_mode = 2;
-      if (b->win_cap == 256) hipLaunchKernelGGL(w4s_segment<256>, dim3((unsigned)b->h_n_big64), dim3(64), 0, b->cur, v, (int64_t)0);
-      else hipLaunchKernelGGL(w4s_segment<SNF_WIN_MAXCAP>, dim3((unsigned)b->h_n_big64), dim3(64), 0, b->cur, v, (int64_t)0);
+      if (b->win_cap == 256) KERNEL_GRID(w4s_segment<256>, big, dim3(64), v, 0, "w4s_segment", 0, none);
+      else KERNEL_GRID(w4s_segment<SNF_WIN_MAXCAP>, big, dim3(64), v, 0, "w4s_segment", 0, none);
       v.w4_mode = 0;
     }
-    else if (b->win_cap == 64) hipLaunchKernelGGL(w4s_segment<64>, dim3((unsigned)n_blk), dim3(64), 0, b->cur, v, (int64_t)0);
-    else if (b->win_cap == 256) hipLaunchKernelGGL(w4s_segment<256>, dim3((unsigned)n_blk), dim3(64), 0, b->cur, v, (int64_t)0);
-    else hipLaunchKernelGGL(w4s_segment<SNF_WIN_MAXCAP>, dim3((unsigned)n_blk), dim3(64), 0, b->cur, v, (int64_t)0);
-    delete sc;
-    SNF_HIP(hipGetLastError());
+    else if (b->win_cap == 64) KERNEL_GRID(w4s_segment<64>, all, dim3(64), v, 0, "w4s_segment", 0, none);
+    else if (b->win_cap == 256) KERNEL_GRID(w4s_segment<256>, all, dim3(64), v, 0, "w4s_segment", 0, none);
+    else KERNEL_GRID(w4s_segment<SNF_WIN_MAXCAP>, all, dim3(64), v, 0, "w4s_segment", 0, none);
   }
-  if (v.chain_on) CHAIN(w5c_offsets, n_blk);
-  else { FUSED(w5a_sums, n_blk); FUSED(w5b_offsets, n_blk); }
-  LAUNCH_Q(w6t_emit, v, N, 0);
+  if (v.chain_on) KERNEL_N(w5c_offsets, v, n_blk, 0, quiet);
+  else { KERNEL_N(w5a_sums, v, n_blk, 0, quiet); KERNEL_N(w5b_offsets, v, n_blk, 0, quiet); }
+  KERNEL_N(w6t_emit, v, N, 0, quiet);
 }
 
 // The byte copies of merge_inner's fused sequences, off the chain: the refine kernels have recorded source, length and destination
@@ -1455,35 +1428,186 @@ void enqueue_fuse_copy(snf_batch_impl* b, hipEvent_t after) {
   if (!after) { SNF_HIP(hipEventRecord(b->ev_refined, b->stream)); after = b->ev_refined; }
   SNF_HIP(hipStreamWaitEvent(b->stream2, after, 0));
   hipStream_t prev = b->cur; b->cur = b->stream2;
-  { Scope _s(b, "d1c_fusecopy", 0);
-    int64_t grid = (v.NS + 63) / 64; if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(d1c_fusecopy, dim3((unsigned)grid), dim3(64), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError()); }
+  int64_t grid = (v.NS + 63) / 64; if (grid > 2048) grid = 2048;
+  KERNEL_GRID(d1c_fusecopy, dim3((unsigned)grid), dim3(64), v, 0, "d1c_fusecopy", 0, heavy);
   b->cur = prev;
   SNF_HIP(hipEventRecord(b->ev_fcopy, b->stream2));
   b->fcopy_open = true;
+}
+
+// ---- the candidate stage, in the order it is enqueued: stages A-C, refine, [read preparation on the side stream], call + compaction,
+// the counters and the side-stream tail.  N: positions behind the sort (the prefilter's count is known since the upload), > 0 in the
+// first three.
+// Stages A-C behind the front end (window front end, or keys + sort): bins, seeds, runs, merged clusters
+void enqueue_clustering(snf_batch_impl* b, bool front) {
+  View& v = b->v;
+  const int64_t N = v.NS; const int T = v.T;
+  if (!b->fused) {
+    uint32_t* tails[] = {v.headflag, v.eligflag, v.fN, v.fL, v.runflag, v.clflag, v.rcflag, v.cdflag};
+    for (auto p : tails) dzero(b, p + N, sizeof(uint32_t));
+  }
+  if (!front) {
+  if (v.key32) prim_sort_pairs<uint32_t>(b, (uint32_t*)v.key_in, (uint32_t*)v.key_out, v.val_in, v.val_out, N, v.key_nbits + 1, "sort_lead_keys");
+  else prim_sort_pairs<uint64_t>(b, v.key_in, v.key_out, v.val_in, v.val_out, N, v.key_nbits + 1, "sort_lead_keys");
+  }
+  if (b->fused) {
+  // flag -> device-wide scan -> emit chains as "flags + tile sums" / "tile prefix + block scan + emit" kernel pairs
+  // (snf_fused.h): 13 launches for stages A-C instead of 26 (each rocPRIM scan is an init kernel + a scan kernel)
+  if (!front) {
+  KERNEL_N(a2k_heads, v, N, 0, quiet);
+  KERNEL_N(a3k_bins, v, N, 0, quiet);
+  { Scope _s(b, "a4_binstats", N * 16); KERNEL_N(a4k_binstats, v, N, 0, quiet); }
+  KERNEL_N(a5k_leadflags, v, N, 0, quiet);
+  { Scope _s(b, "a6_scatter", N * 16); KERNEL_N(a6k_scatter, v, N, 0, quiet); }
+  KERNEL_N(a7k_seeds, v, N, 0, quiet);
+  }
+  if (v.chain_on) { Scope _s(b, "b1_seedmetrics", N * 8); KERNEL_N(b12c_seedruns, v, N, 0, quiet); }
+  else {
+  { Scope _s(b, "b1_seedmetrics", N * 8); KERNEL_N(b1k_seedmetrics, v, N, 0, quiet); }
+  KERNEL_N(b2k_runs, v, N, 0, quiet);
+  }
+  KERNEL_N(c1_mergeruns, v, N, N * 8, heavy);
+  KERNEL_N(c2_validate, v, N, 0, quiet);
+  KERNEL_N(c3_serial, v, 8 * (int64_t)T, 0, quiet);
+  if (v.chain_on) KERNEL_N(c4c_clusters, v, N, 0, quiet);
+  else {
+  KERNEL_N(c4a_count, v, N, 0, quiet);
+  KERNEL_N(c4k_clusters, v, N, 0, quiet);
+  }
+  } else {
+  KERNEL_N(a2_heads, v, N, N * 12, quiet);
+  prim_exscan<uint32_t>(b, v.headflag, v.headscan, N + 1, "scan_bins");
+  KERNEL_N(a3_bins, v, N, N * 8, quiet);
+  KERNEL_N(a4_binstats, v, N, N * 16, heavy);
+  prim_exscan<uint32_t>(b, v.eligflag, v.eligscan, N + 1, "scan_seeds");
+  KERNEL_N(a5_leadflags, v, N, N * 12, quiet);
+  prim_exscan<uint32_t>(b, v.fN, v.pN, N + 1, "scan_leads");
+  prim_exscan<uint32_t>(b, v.fL, v.pL, N + 1, "scan_leads_long");
+  KERNEL_N(a6_scatter, v, N, N * 16, quiet);
+  KERNEL_N(a7_seeds, v, N, N * 4, quiet);
+  KERNEL_N(b1_seedmetrics, v, N, N * 8, heavy);
+  prim_exscan<uint32_t>(b, v.runflag, v.runscan, N + 1, "scan_runs");
+  KERNEL_N(b2_runs, v, N, N * 4, quiet);
+  KERNEL_N(c1_mergeruns, v, N, N * 8, heavy);
+  KERNEL_N(c2_validate, v, N, 0, quiet);
+  KERNEL_N(c3_serial, v, 8 * (int64_t)T, 0, quiet);
+  prim_exscan<uint32_t>(b, v.clflag, v.clscan, N + 1, "scan_clusters");
+  KERNEL_N(c4_clusters, v, N, N * 4, quiet);
+  dzero(b, v.rcflag, sizeof(uint32_t) * (N + 1));
+  }
+}
+// merge_inner / resplit of every cluster
+void enqueue_refine(snf_batch_impl* b) {
+  View& v = b->v;
+  const int64_t N = v.NS;
+  const dim3 grid(b->slots_d1w);
+  const auto d1w = v.fuse_defer ? d1w_refine<true> : d1w_refine<false>;
+  if (v.wave_path && b->k.d1_groups) {
+    // merge_inner / resplit by cluster size (snf_wave_refine_g.h): eight clusters of <= 8 leads per wave, and d1w_refine - a wave
+    // per cluster - for the others, which c4_emit has listed.  The two share no cluster and no output entry: in an eager pass the
+    // grouped kernel goes beside the other one (ClassFork), in a captured pass they stay in line
+    { ClassFork _f(b);
+      KERNEL_GRID((v.fuse_defer ? d1g_refine<8, true> : d1g_refine<8, false>), grid, dim3(64), v, 0, "d1g_refine8", N * 36 / 3, heavy); }
+    v.d1_from_list = 1;
+    KERNEL_GRID(d1w, grid, dim3(64), v, 0, "d1w_refine", N * 36 - N * 36 / 3, heavy);
+    v.d1_from_list = 0;
+    join_classes(b);      // (x_big<0> and the rc table need both)
+  } else if (v.wave_path)
+    KERNEL_GRID(d1w, grid, dim3(64), v, 0, "d1w_refine", N * 36, heavy);
+  if (!(v.wave_path && b->fused)) KERNEL_N(d1_refine, v, N, v.wave_path ? 0 : N * 36, quiet);   // (next to the wave kernels every item would return at once)
+  b->skipped_big[0] = b->skipped_big[1] = b->skipped_big[2] = false;
+  if (v.wave_path && b->have_big_hist && b->hist_big[0] == 0) b->skipped_big[0] = true;      // (same input: no cluster of more than 64 leads)
+  else if (v.wave_path) KERNEL_GRID(x_big<0>, dim3(b->slots_big), dim3(64), v, 0, "x_big_refine", 0, heavy);   // clusters of more than 64 leads, one wave each
+}
+// the refined-cluster table, call_from of every refined cluster, the candidates compacted
+void enqueue_call(snf_batch_impl* b) {
+  View& v = b->v;
+  const int64_t N = v.NS;
+  const bool ph = b->cfg.phase != 0;
+  const dim3 grid(b->slots_d2w);
+  const auto d2w = ph ? d2w_call<5, true> : d2w_call<5, false>;
+  if (b->fused && v.chain_on) KERNEL_N(d1bc_rctable, v, N, 0, quiet);
+  else if (b->fused) KERNEL_N(d1bk_rctable, v, N, 0, quiet);      // (the tile sums of rcflag: published by rc_emit)
+  else {
+    prim_exscan<uint32_t>(b, v.rcflag, v.rcscan, N + 1, "scan_refined");
+    KERNEL_N(d1b_rctable, v, N, N * 4, quiet);
+  }
+  // (the fused sequences' copies go to the side stream here, behind the read preparation, which need not wait for the refine kernels)
+  const bool call_forks = v.wave_path && b->k.d2_groups && classes_beside(b);
+  if (v.fuse_defer && !call_forks) enqueue_fuse_copy(b, nullptr);
+  if (v.wave_path && b->k.d2_groups) {
+    // call_from by cluster size (snf_wave_call_g.h): eight clusters of <= 8 leads per wave; d2w_call - a wave per cluster - for the
+    // others, from the list d1b_emit built (with the mid class: two of <= 32 per wave from list 0, d2w_call from list 1).  As in the
+    // refine stage the grouped kernel of an eager pass runs beside the others
+    // (32 B per signature for the call stage, split by the share of the leads each kernel sees on a 30x genome - a third of
+    //  them sit in refined clusters of at most eight leads)
+    { ClassFork _f(b);
+      KERNEL_GRID((ph ? d2g_call<8, 4, true> : d2g_call<8, 4, false>), grid, dim3(64), v, 0, "d2g_call8", N * 32 / 3, heavy); }
+    if (v.fuse_defer && call_forks) enqueue_fuse_copy(b, b->ev_cls_fork);      // (the event ClassFork has just recorded behind d1bk_rctable)
+    const bool mid = b->k.d2_mid;
+    if (mid) KERNEL_GRID((ph ? d2g_call<32, 4, true> : d2g_call<32, 4, false>), grid, dim3(64), v, 0, "d2g_call32", 0, heavy);
+    v.d2_from_list = mid ? 2 : 1;
+    KERNEL_GRID(d2w, grid, dim3(64), v, 0, "d2w_call", N * 32 - N * 32 / 3, heavy);
+    v.d2_from_list = 0;
+    join_classes(b);      // (x_big<1> and the compaction need both)
+  } else if (v.wave_path)
+    KERNEL_GRID(d2w, grid, dim3(64), v, 0, "d2w_call", N * 32, heavy);
+  if (!(v.wave_path && b->fused)) KERNEL_N(d2_call, v, N, v.wave_path ? 0 : N * 32, quiet);
+  if (v.wave_path && b->have_big_hist && b->hist_big[1] == 0) b->skipped_big[1] = true;
+  else if (v.wave_path) KERNEL_GRID(x_big<1>, dim3(b->slots_big), dim3(64), v, 0, "x_big_call", 0, heavy);
+  if (b->fused && v.chain_on) KERNEL_N(d3cc_compact, v, N, 0, quiet);
+  else if (b->fused) KERNEL_N(d3ck_compact, v, N, 0, quiet);      // (the tile sums of cdflag: published where a candidate is written)
+  else {
+    prim_exscan<uint32_t>(b, v.cdflag, v.cdscan, N + 1, "scan_calls");
+    KERNEL_N(d3_compact, v, N, 0, quiet);
+  }
+}
+void enqueue_candidate_tail(snf_batch_impl* b) {
+  View& v = b->v;
+  const int64_t N = v.NS;
+  // the number of calls is known here: publish the counters (pinned block) and let the host pick them up through
+  // ev_counts.  Nothing the ALT chain of finalize needs is produced after this point, so the rest of the candidate
+  // stage (sv ids, supporting read names, coverage annotation) continues on the side stream, behind the read preparation
+  KERNEL_N(d3_taskoff, v, tail_threads(v), 0, quiet);
+  SNF_HIP(hipEventRecord(b->ev_counts, b->stream));
+  fork_mark(b);
+  if (b->fused) {
+    {  // sv ids + supporting read names: own stream (nothing on the coverage -> QC -> record copy chain waits for them
+       // except the copy itself, through ev_rn)
+      SNF_HIP(hipStreamWaitEvent(b->stream4, b->ev_fork, 0));
+      hipStream_t prev = b->cur; b->cur = b->stream4;
+      if (N > 0 && v.chain_on) { Scope _s(b, "d3_rnames", 0); KERNEL_N(d3src_svid_rnames, v, N, 0, quiet); }
+      else if (N > 0) {
+        KERNEL_N(d3sk_svid, v, N, 0, quiet);
+        { Scope _s(b, "d3_rnames", 0); KERNEL_N(d3rk_rnames, v, N, 0, quiet); }
+      } else *b->h_rn_total = 0;
+      SNF_HIP(hipEventRecord(b->ev_rn, b->stream4));
+      b->cur = prev;
+    }
+    SideStream side(b);
+    if (N > 0) launch_coverage(b, N);
+  } else
+  {
+    SideStream side(b);
+    if (N > 0) {
+      KERNEL_N(d3_svid, v, N, 0, quiet);
+      prim_exscan<uint32_t>(b, v.rnf, v.rnp, N + 1, "scan_rnames");
+      KERNEL_N(d3_rnames, v, N, 0, heavy);
+    } else *b->h_rn_total = 0;
+    SNF_HIP(hipEventRecord(b->ev_rn, b->cur));
+    if (N > 0) launch_coverage(b, N);
+  }
 }
 
 void run_call_candidates(snf_batch_impl* b) {
   SNF_TRACE("snf_batch_call_candidates (enqueue)");
   b->pass_idle = false;
   View& v = b->v;
-  int T = v.T;
   const int64_t N = v.NS;   // positions behind the sort (the prefilter's count is known since the upload)
   b->reads_ready = true; b->cov_avg_ready = true; b->finalized = false;
   begin_pass_timing(b);
   pass_begins(b);
   join_open_candidates(b);
-  b->chain_slot = -1;
-  if (process_knobs().chain_gate && !b->capturing) {
-    DevicePacing& P = pacing_of(b);
-    std::lock_guard<std::mutex> g(P.pace_mu);
-    const unsigned long long my = P.chain_seq++;
-    hipEvent_t& mine = P.chain_ev[my & 1]; hipEvent_t prev = P.chain_ev[(my + 1) & 1];
-    if (!mine) SNF_HIP(hipEventCreateWithFlags(&mine, hipEventDisableTiming));
-    b->chain_slot = (int)(my & 1);
-    if (prev && P.passes_in_flight.load() > 1) SNF_HIP(hipStreamWaitEvent(b->stream, prev, 0));
-  }
   // SNF_OUT_EXECUTE (set before this call): the names of the supporting reads are only written for the calls that pass QC,
   // once finalize knows them (a stage-0 fetch writes them all, late)
   v.rn_defer = ((v.out_mode & SNF_OUT_EXECUTE) && !v.cfg.no_qc && b->k.rn_defer && b->k.fuse && N <= ((int64_t)1 << 25)) ? 1 : 0;
@@ -1495,180 +1619,16 @@ void run_call_candidates(snf_batch_impl* b) {
   if (v.wave_path && !b->fused) dzero(b, v.big_cnt, sizeof(uint32_t) * 3 * 64 * 16);   // (fused: z0_init)
   if (v.wave_path && !b->fused) dzero(b, v.d2cnt, sizeof(uint32_t) * 3 * 64 * 16);
   b->finalize_runs = 0;
-  fork_mark(b);  // the read-preparation branch may start here, wherever it is enqueued below
-  if (b->k.readprep == 0) enqueue_read_prep(b);
+  fork_mark(b);  // the read-preparation branch may start here, although it is only enqueued behind the refine kernels below
   const bool front = v.front && b->fused && N > 0;
   if (front) enqueue_window_front(b); else enqueue_keys(b);
   if (N > 0) {
-    if (!b->fused) {
-      uint32_t* tails[] = {v.headflag, v.eligflag, v.fN, v.fL, v.runflag, v.clflag, v.rcflag, v.cdflag};
-      for (auto p : tails) dzero(b, p + N, sizeof(uint32_t));
-    }
-    if (!front) {
-    if (v.key32) prim_sort_pairs<uint32_t>(b, (uint32_t*)v.key_in, (uint32_t*)v.key_out, v.val_in, v.val_out, N, v.key_nbits + 1, "sort_lead_keys");
-    else prim_sort_pairs<uint64_t>(b, v.key_in, v.key_out, v.val_in, v.val_out, N, v.key_nbits + 1, "sort_lead_keys");
-    }
-    if (b->fused) {
-    // flag -> device-wide scan -> emit chains as "flags + tile sums" / "tile prefix + block scan + emit" kernel pairs
-    // (snf_fused.h): 13 launches for stages A-C instead of 26 (each rocPRIM scan is an init kernel + a scan kernel)
-    if (!front) {
-    FUSED(a2k_heads, N);
-    FUSED(a3k_bins, N);
-    { Scope _s(b, "a4_binstats", N * 16); FUSED(a4k_binstats, N); }
-    FUSED(a5k_leadflags, N);
-    { Scope _s(b, "a6_scatter", N * 16); FUSED(a6k_scatter, N); }
-    FUSED(a7k_seeds, N);
-    }
-    if (v.chain_on) { Scope _s(b, "b1_seedmetrics", N * 8); CHAIN(b12c_seedruns, N); }
-    else {
-    { Scope _s(b, "b1_seedmetrics", N * 8); FUSED(b1k_seedmetrics, N); }
-    FUSED(b2k_runs, N);
-    }
-    LAUNCH(c1_mergeruns, v, N, N * 8);
-    LAUNCH_Q(c2_validate, v, N, 0);
-    LAUNCH_Q(c3_serial, v, 8 * (int64_t)T, 0);
-    if (v.chain_on) CHAIN(c4c_clusters, N);
-    else {
-    FUSED(c4a_count, N);
-    FUSED(c4k_clusters, N);
-    }
-    } else {
-    LAUNCH_Q(a2_heads, v, N, N * 12);
-    prim_exscan<uint32_t>(b, v.headflag, v.headscan, N + 1, "scan_bins");
-    LAUNCH_Q(a3_bins, v, N, N * 8);
-    LAUNCH(a4_binstats, v, N, N * 16);
-    prim_exscan<uint32_t>(b, v.eligflag, v.eligscan, N + 1, "scan_seeds");
-    LAUNCH_Q(a5_leadflags, v, N, N * 12);
-    prim_exscan<uint32_t>(b, v.fN, v.pN, N + 1, "scan_leads");
-    prim_exscan<uint32_t>(b, v.fL, v.pL, N + 1, "scan_leads_long");
-    LAUNCH_Q(a6_scatter, v, N, N * 16);
-    LAUNCH_Q(a7_seeds, v, N, N * 4);
-    LAUNCH(b1_seedmetrics, v, N, N * 8);
-    prim_exscan<uint32_t>(b, v.runflag, v.runscan, N + 1, "scan_runs");
-    LAUNCH_Q(b2_runs, v, N, N * 4);
-    LAUNCH(c1_mergeruns, v, N, N * 8);
-    LAUNCH_Q(c2_validate, v, N, 0);
-    LAUNCH_Q(c3_serial, v, 8 * (int64_t)T, 0);
-    prim_exscan<uint32_t>(b, v.clflag, v.clscan, N + 1, "scan_clusters");
-    LAUNCH_Q(c4_clusters, v, N, N * 4);
-    dzero(b, v.rcflag, sizeof(uint32_t) * (N + 1));
-    }
-    if (b->k.readprep == 3) fork_mark(b);   // mode 3: the read preparation may only start once stages A-C are through
-    if (v.wave_path && b->k.d1_groups) {
-      // merge_inner / resplit by cluster size (snf_wave_refine_g.h): eight clusters of <= 8 leads per wave, and d1w_refine - a wave
-      // per cluster - for the others, which c4_emit has listed.  The two share no cluster and no output entry: in an eager pass the
-      // grouped kernel goes beside the other one (ClassFork), in a captured pass they stay in line
-      { ClassFork _f(b);
-        Scope _s(b, "d1g_refine8", N * 36 / 3);
-        hipLaunchKernelGGL((v.fuse_defer ? d1g_refine<8, true> : d1g_refine<8, false>), dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
-        SNF_HIP(hipGetLastError()); }
-      { Scope _s(b, "d1w_refine", N * 36 - N * 36 / 3);
-        v.d1_from_list = 1;
-        hipLaunchKernelGGL((v.fuse_defer ? d1w_refine<true> : d1w_refine<false>), dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
-        v.d1_from_list = 0;
-        SNF_HIP(hipGetLastError()); }
-      join_classes(b);      // (x_big<0> and the rc table need both)
-    } else if (v.wave_path) {
-      Scope _s(b, "d1w_refine", N * 36);
-      hipLaunchKernelGGL((v.fuse_defer ? d1w_refine<true> : d1w_refine<false>), dim3(b->slots_d1w), dim3(64), 0, b->cur, v, (int64_t)0);
-      SNF_HIP(hipGetLastError());
-    }
-    if (!(v.wave_path && b->fused)) LAUNCH_Q(d1_refine, v, N, v.wave_path ? 0 : N * 36);   // (next to the wave kernels every item would return at once)
-    b->skipped_big[0] = b->skipped_big[1] = b->skipped_big[2] = false;
-    if (v.wave_path && b->have_big_hist && b->hist_big[0] == 0) b->skipped_big[0] = true;      // (same input: no cluster of more than 64 leads)
-    else if (v.wave_path) {   // clusters of more than 64 leads, one wave each
-      Scope _s(b, "x_big_refine", 0);
-      hipLaunchKernelGGL(x_big<0>, dim3(b->slots_big), dim3(64), 0, b->cur, v, (int64_t)0);
-      SNF_HIP(hipGetLastError());
-    }
+    enqueue_clustering(b, front);
+    enqueue_refine(b);
   }
-  if (b->k.readprep == 1 || b->k.readprep == 3) enqueue_read_prep(b);  // while the long refine kernel keeps the main stream busy
-  if (N > 0) {
-    if (b->fused && v.chain_on) CHAIN(d1bc_rctable, N);
-    else if (b->fused) FUSED(d1bk_rctable, N);      // (the tile sums of rcflag: published by rc_emit)
-    else {
-      prim_exscan<uint32_t>(b, v.rcflag, v.rcscan, N + 1, "scan_refined");
-      LAUNCH_Q(d1b_rctable, v, N, N * 4);
-    }
-    // (the fused sequences' copies go to the side stream here, behind the read preparation, which need not wait for the refine kernels)
-    const bool call_forks = v.wave_path && b->k.d2_groups && classes_beside(b);
-    if (v.fuse_defer && !call_forks) enqueue_fuse_copy(b, nullptr);
-    if (v.wave_path && b->k.d2_groups) {
-      // call_from by cluster size (snf_wave_call_g.h): eight clusters of <= 8 leads per wave; d2w_call - a wave per cluster - for the
-      // others, from the list d1b_emit built (with the mid class: two of <= 32 per wave from list 0, d2w_call from list 1).  As in the
-      // refine stage the grouped kernel of an eager pass runs beside the others
-      const bool ph = b->cfg.phase != 0;
-      // (32 B per signature for the call stage, split by the share of the leads each kernel sees on a 30x genome - a third of
-      //  them sit in refined clusters of at most eight leads)
-      { ClassFork _f(b);
-        Scope _s(b, "d2g_call8", N * 32 / 3);
-        if (ph) hipLaunchKernelGGL((d2g_call<8, 4, true>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
-        else hipLaunchKernelGGL((d2g_call<8, 4, false>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
-        SNF_HIP(hipGetLastError()); }
-      if (v.fuse_defer && call_forks) enqueue_fuse_copy(b, b->ev_cls_fork);      // (the event ClassFork has just recorded behind d1bk_rctable)
-      const bool mid = b->k.d2_mid;
-      if (mid) { Scope _s(b, "d2g_call32", 0);
-        if (ph) hipLaunchKernelGGL((d2g_call<32, 4, true>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
-        else hipLaunchKernelGGL((d2g_call<32, 4, false>), dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
-        SNF_HIP(hipGetLastError()); }
-      { Scope _s(b, "d2w_call", N * 32 - N * 32 / 3);
-        v.d2_from_list = mid ? 2 : 1;
-        hipLaunchKernelGGL(b->k_d2w, dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
-        v.d2_from_list = 0;
-        SNF_HIP(hipGetLastError()); }
-      join_classes(b);      // (x_big<1> and the compaction need both)
-    } else if (v.wave_path) {
-      Scope _s(b, "d2w_call", N * 32);
-      hipLaunchKernelGGL(b->k_d2w, dim3(b->slots_d2w), dim3(64), 0, b->cur, v, (int64_t)0);
-      SNF_HIP(hipGetLastError());
-    }
-    if (!(v.wave_path && b->fused)) LAUNCH_Q(d2_call, v, N, v.wave_path ? 0 : N * 32);
-    if (v.wave_path && b->have_big_hist && b->hist_big[1] == 0) b->skipped_big[1] = true;
-    else if (v.wave_path) {
-      Scope _s(b, "x_big_call", 0);
-      hipLaunchKernelGGL(x_big<1>, dim3(b->slots_big), dim3(64), 0, b->cur, v, (int64_t)0);
-      SNF_HIP(hipGetLastError());
-    }
-    if (b->fused && v.chain_on) CHAIN(d3cc_compact, N);
-    else if (b->fused) FUSED(d3ck_compact, N);      // (the tile sums of cdflag: published where a candidate is written)
-    else {
-      prim_exscan<uint32_t>(b, v.cdflag, v.cdscan, N + 1, "scan_calls");
-      LAUNCH_Q(d3_compact, v, N, 0);
-    }
-  }
-  // the number of calls is known here: publish the counters (pinned block) and let the host pick them up through
-  // ev_counts.  Nothing the ALT chain of finalize needs is produced after this point, so the rest of the candidate
-  // stage (sv ids, supporting read names, coverage annotation) continues on the side stream, behind the read preparation
-  LAUNCH_Q(d3_taskoff, v, tail_threads(v), 0);
-  SNF_HIP(hipEventRecord(b->ev_counts, b->stream));
-  if (b->k.readprep == 2) enqueue_read_prep(b);
-  fork_mark(b);
-  if (b->fused) {
-    {  // sv ids + supporting read names: own stream (nothing on the coverage -> QC -> record copy chain waits for them
-       // except the copy itself, through ev_rn)
-      SNF_HIP(hipStreamWaitEvent(b->stream4, b->ev_fork, 0));
-      hipStream_t prev = b->cur; b->cur = b->stream4;
-      if (N > 0 && v.chain_on) { Scope _s(b, "d3_rnames", 0); CHAIN(d3src_svid_rnames, N); }
-      else if (N > 0) {
-        FUSED(d3sk_svid, N);
-        { Scope _s(b, "d3_rnames", 0); FUSED(d3rk_rnames, N); }
-      } else *b->h_rn_total = 0;
-      SNF_HIP(hipEventRecord(b->ev_rn, b->stream4));
-      b->cur = prev;
-    }
-    SideStream side(b);
-    if (N > 0) launch_coverage(b, N);
-  } else
-  {
-    SideStream side(b);
-    if (N > 0) {
-      LAUNCH_Q(d3_svid, v, N, 0);
-      prim_exscan<uint32_t>(b, v.rnf, v.rnp, N + 1, "scan_rnames");
-      LAUNCH(d3_rnames, v, N, 0);
-    } else *b->h_rn_total = 0;
-    SNF_HIP(hipEventRecord(b->ev_rn, b->cur));
-    if (N > 0) launch_coverage(b, N);
-  }
+  enqueue_read_prep(b);  // while the long refine kernel keeps the main stream busy
+  if (N > 0) enqueue_call(b);
+  enqueue_candidate_tail(b);
   b->res_current = false;
   v.out_valid = 0;
   b->side_open = true;
@@ -1692,7 +1652,7 @@ void join_open_candidates(snf_batch_impl* b) {
 void full_sync(snf_batch_impl* b) {
   join_side(b);
   join_fourth(b);
-  if (!b->res_current) { LAUNCH_Q(z1_results, b->v, tail_threads(b->v), 0); b->res_current = true; }
+  if (!b->res_current) { KERNEL_N(z1_results, b->v, tail_threads(b->v), 0, quiet); b->res_current = true; }
   dsync(b);
 }
 
@@ -1712,10 +1672,8 @@ void enqueue_rnames_late(snf_batch_impl* b, bool all) {
   if (b->rn_state == 0 || (b->rn_state == 2 && !all) || v.NS <= 0) return;
   const int keep = v.rn_defer;
   v.rn_defer = all ? 2 : 1;
-  { Scope _s(b, "d3_rnames_late", 0);
-    unsigned grid = (unsigned)((v.NS / 4 + 255) / 256) + 1u; if (grid > 4096u) grid = 4096u;
-    hipLaunchKernelGGL(d3lk_rnames_late, dim3(grid), dim3(256), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError()); }
+  unsigned grid = (unsigned)((v.NS / 4 + 255) / 256) + 1u; if (grid > 4096u) grid = 4096u;
+  KERNEL_GRID(d3lk_rnames_late, dim3(grid), dim3(256), v, 0, "d3_rnames_late", 0, heavy);
   v.rn_defer = keep;
   b->rn_state = all ? 0 : 2;
 }
@@ -1731,28 +1689,24 @@ void enqueue_output_head(snf_batch_impl* b) {
   if (!rn_src) enqueue_rnames_late(b, rn_all);
   if (b->fused && NS <= ((int64_t)1 << 22) * 256) {
     const unsigned grid = (unsigned)((NS + 255) / 256) > 0u ? (unsigned)((NS + 255) / 256) : 1u;
-    FUSED(f1k_outflags, NS > 0 ? NS : 1);
-    FUSED(f2k_outscan, NS > 0 ? NS : 1);
+    KERNEL_N(f1k_outflags, v, NS > 0 ? NS : 1, 0, quiet);
+    KERNEL_N(f2k_outscan, v, NS > 0 ? NS : 1, 0, quiet);
     if ((v.out_mode & SNF_OUT_EXECUTE) && v.cfg.sort) {
-      Scope _s(b, "f3_rank", 0);
       const unsigned g3 = grid * (256u / F3_Q);      // a workgroup per F3_Q calls of the upper bound
-      hipLaunchKernelGGL(f3k_rank, dim3(g3 < 4096u ? g3 : 4096u), dim3(256), 0, b->cur, v, (int64_t)0);
-      SNF_HIP(hipGetLastError());
+      KERNEL_GRID(f3k_rank, dim3(g3 < 4096u ? g3 : 4096u), dim3(256), v, 0, "f3_rank", 0, heavy);
     }
-    { Scope _s(b, "f4_emit", 0);
-      v.rn_from_src = rn_src ? 1 : 0;
-      const unsigned f4cap = (unsigned)b->k.f4_grid;
-      hipLaunchKernelGGL(f4w_emit, dim3(grid < f4cap ? grid : f4cap), dim3(256), 0, b->cur, v, (int64_t)0);
-      v.rn_from_src = 0;
-      SNF_HIP(hipGetLastError()); }
+    constexpr unsigned F4_GRID_CAP = 2048;           // f4w_emit strides beyond this many workgroups
+    v.rn_from_src = rn_src ? 1 : 0;
+    KERNEL_GRID(f4w_emit, dim3(grid < F4_GRID_CAP ? grid : F4_GRID_CAP), dim3(256), v, 0, "f4_emit", 0, heavy);
+    v.rn_from_src = 0;
   } else {
     const int64_t nc = NS;   // upper bound of the number of calls (the bodies stop at the device's count)
-    LAUNCH_Q(f1_flags, v, nc + 1, 0);
+    KERNEL_N(f1_flags, v, nc + 1, 0, quiet);
     prim_exscan<uint32_t>(b, v.o_scan, v.pL, nc + 1, "scan_out");
     prim_exscan<int64_t>(b, v.sz_rd, v.sc_rd, nc + 1, "scan_out");
-    LAUNCH_Q(f2_scan, v, nc + 1, 0);
-    if ((v.out_mode & SNF_OUT_EXECUTE) && v.cfg.sort) LAUNCH_Q(f3_rank, v, nc, 0);
-    LAUNCH_Q(f4_emit, v, nc, 0);
+    KERNEL_N(f2_scan, v, nc + 1, 0, quiet);
+    if ((v.out_mode & SNF_OUT_EXECUTE) && v.cfg.sort) KERNEL_N(f3_rank, v, nc, 0, quiet);
+    KERNEL_N(f4_emit, v, nc, 0, quiet);
   }
 }
 // Thread-kernel form of the ALT stage (e4 / e5 / e6) and the ROWS instance need scratch sized by totals that only the device
@@ -1779,16 +1733,14 @@ void run_alt_fallback(snf_batch_impl* b) {
   ensure_cap(b, nreads, r3, (void**)&v.cr_read, sizeof(int32_t));
   b->cr_cap = r1;
   const bool threads = !v.wave_path || c.n_cons_fallback > 0;
-  if (threads) LAUNCH_Q(e4_anchor, v, c.n_cons, v.wave_path ? 0 : c.tab_total * 13);
+  if (threads) KERNEL_N(e4_anchor, v, c.n_cons, v.wave_path ? 0 : c.tab_total * 13, quiet);
   if (v.wave_path && c.n_cls[7] > 0) {   // work list 7: calls beyond the LDS vote counters and what SMALL / LARGE handed over at run time
-    Scope _s(b, "e45w_consensus_rows", 0);
     const int64_t n_rows = (int64_t)c.n_cls[7];
-    hipLaunchKernelGGL((K_CONS_ROWS), dim3((unsigned)(n_rows < 16384 ? n_rows : 16384)), dim3(256), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError());
+    KERNEL_GRID((K_CONS_ROWS), dim3((unsigned)(n_rows < 16384 ? n_rows : 16384)), dim3(256), v, 0, "e45w_consensus_rows", 0, heavy);
   }
   if (threads) {
-    LAUNCH_Q(e5_align, v, c.n_cons_reads, v.wave_path ? 0 : c.aln_total * 2);
-    LAUNCH(e6_vote, v, c.alt_total, c.aln_total + 2 * c.alt_total);
+    KERNEL_N(e5_align, v, c.n_cons_reads, v.wave_path ? 0 : c.aln_total * 2, quiet);
+    KERNEL_N(e6_vote, v, c.alt_total, c.aln_total + 2 * c.alt_total, heavy);
   }
 }
 
@@ -1806,27 +1758,21 @@ void enqueue_consensus_wave(snf_batch_impl* b, int64_t g_small, int64_t g_large,
   // pass in flight that pass fills the tails instead (two in flight: 1.238 against 1.242).  So: 2 when another pass is in flight on
   // the device, 0 otherwise; SNF_CONS_ORDER forces one (1 = SMALL behind LARGE: slower than both).
   const int order = b->k.cons_order >= 0 ? b->k.cons_order : (pacing_of(b).passes_in_flight.load() > 1 ? 2 : 0);
+  // The consensus kernels take one call per workgroup from the hardware dispatcher: plain grids (resident grids that stride or claim
+  // calls from a counter were measured slower: DESIGN.md, "Retired switches").  Only the one-wave SMALL kernel strides, beyond SMALL_1W_CAP
+  constexpr int64_t GRID_CAP = 1 << 22, SMALL_1W_CAP = 65536;
   auto launch_large = [&]() {
-    Scope _s(b, "e45w_consensus_large", 0, true);
-    const dim3 gl((unsigned)(g_large < b->slots_cons_l ? g_large : b->slots_cons_l));
-    if (b->k.cons_large_nw == 16) hipLaunchKernelGGL((K_CONS_LARGE_16W), gl, dim3(1024), 0, b->cur, v, (int64_t)0);
-    else if (b->k.cons_large_nw == 8) hipLaunchKernelGGL((K_CONS_LARGE_8W), gl, dim3(512), 0, b->cur, v, (int64_t)0);
-    else hipLaunchKernelGGL((K_CONS_LARGE), gl, dim3(256), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError());
+    const dim3 gl((unsigned)(g_large < GRID_CAP ? g_large : GRID_CAP));
+    if (b->k.cons_large_nw == 16) KERNEL_GRID((K_CONS_LARGE_16W), gl, dim3(1024), v, 0, "e45w_consensus_large", 0, always);
+    else if (b->k.cons_large_nw == 8) KERNEL_GRID((K_CONS_LARGE_8W), gl, dim3(512), v, 0, "e45w_consensus_large", 0, always);
+    else KERNEL_GRID((K_CONS_LARGE), gl, dim3(256), v, 0, "e45w_consensus_large", 0, always);
   };
   auto launch_small = [&]() {
-    Scope _s(b, "e45w_consensus_small", 0);
-    const dim3 gs((unsigned)(g_small < b->slots_cons_s ? g_small : b->slots_cons_s));
-    if (b->k.cons_nw == 1) hipLaunchKernelGGL((K_CONS_SMALL_1W), dim3((unsigned)(g_small < b->slots_cons_s1 ? g_small : b->slots_cons_s1)), dim3(64), 0, b->cur, v, (int64_t)0);
-    else if (b->k.occ_s >= 8) hipLaunchKernelGGL((K_CONS_SMALL(8)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
-    else if (b->k.occ_s == 6) hipLaunchKernelGGL((K_CONS_SMALL(6)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
-    else hipLaunchKernelGGL((K_CONS_SMALL(5)), gs, dim3(256), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError());
+    if (b->k.cons_nw == 1) KERNEL_GRID((K_CONS_SMALL_1W), dim3((unsigned)(g_small < SMALL_1W_CAP ? g_small : SMALL_1W_CAP)), dim3(64), v, 0, "e45w_consensus_small", 0, heavy);
+    else KERNEL_GRID((K_CONS_SMALL(5)), dim3((unsigned)(g_small < GRID_CAP ? g_small : GRID_CAP)), dim3(256), v, 0, "e45w_consensus_small", 0, heavy);
   };
   auto launch_copy = [&]() {    // verbatim ALTs: short; on the main stream ahead of SMALL
-    Scope _s(b, "e4c_copy", 0);
-    hipLaunchKernelGGL(e4c_copy, dim3((unsigned)(g_copy < 32768 ? g_copy : 32768)), dim3(64), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError());
+    KERNEL_GRID(e4c_copy, dim3((unsigned)(g_copy < 32768 ? g_copy : 32768)), dim3(64), v, 0, "e4c_copy", 0, heavy);
   };
   auto on_stream3 = [&](auto&& f) { hipStream_t prev = b->cur; b->cur = b->stream3; f(); b->cur = prev; };
   // LARGE - the longer chain - stays on the main stream, right behind the kernel that built its work lists: a kernel behind a
@@ -1854,16 +1800,12 @@ void enqueue_consensus_wave(snf_batch_impl* b, int64_t g_small, int64_t g_large,
 // (64 workgroups: enough stores in flight for the PCIe link, a handful of wave slots)
 void stage_copy_block(snf_batch_impl* b) {
   if (!b->staged_kernel || !b->v.stage_out_pin) return;
-  Scope _s(b, "d2h_block", 0);
-  hipLaunchKernelGGL(z2_stage_copy, dim3(64), dim3(256), 0, b->cur, b->v, (int64_t)0);
-  SNF_HIP(hipGetLastError());
+  KERNEL_GRID(z2_stage_copy, dim3(64), dim3(256), b->v, 0, "d2h_block", 0, heavy);
   b->stage_block_copied = true;
 }
 void stage_copy_alt(snf_batch_impl* b) {
   if (!b->staged_kernel || !b->v.stage_alt_pin) return;
-  Scope _s(b, "d2h_alt", 0);
-  hipLaunchKernelGGL(z2_stage_copy, dim3(64), dim3(256), 0, b->cur, b->v, (int64_t)1);
-  SNF_HIP(hipGetLastError());
+  KERNEL_GRID(z2_stage_copy, dim3(64), dim3(256), b->v, 1, "d2h_alt", 0, heavy);
   b->stage_alt_copied = true;
 }
 
@@ -1874,12 +1816,6 @@ void run_finalize(snf_batch_impl* b) {
   const int64_t NS = v.NS;
   b->finalized = true;
   b->res_current = false;
-  if (b->chain_slot >= 0 && !b->capturing) {      // the chain of this pass ends here: the next pass of the device may start its own
-    DevicePacing& P = pacing_of(b);
-    std::lock_guard<std::mutex> g(P.pace_mu);
-    if (P.chain_ev[b->chain_slot]) SNF_HIP(hipEventRecord(P.chain_ev[b->chain_slot], b->stream));
-    b->chain_slot = -1;
-  }
   // Nothing below waits for the device: grids cover upper bounds derived from NS (the kernels read the real counts in HBM
   // and stride or return), the ALT bytes go to an HBM pool sized at upload, and the fetch is the one host wait of the pass.
   {  // pinned block for the result: sized from the input, grown by the fetch when a result did not fit
@@ -1902,9 +1838,8 @@ void run_finalize(snf_batch_impl* b) {
     // ALT section: an eighth of the input sequence bytes (a 30x genome needs a twentieth); the fetch grows it when a pass overflowed into HBM
     const size_t want_alt = (size_t)(v.pool_len / 8) + ((size_t)1 << 20);
     if (!(v.out_mode & SNF_OUT_DEVICE) && !b->hb_alt.external && b->hb_alt.cap < want_alt) b->hb_alt.ensure(want_alt);
-    const bool alt_hbm = b->k.alt_hbm || stage;
-    v.alt_pin = ((v.out_mode & SNF_OUT_DEVICE) || alt_hbm) ? nullptr : (uint8_t*)b->hb_alt.p;
-    v.alt_pin_cap = ((v.out_mode & SNF_OUT_DEVICE) || alt_hbm) ? 0 : (int64_t)b->hb_alt.cap;
+    v.alt_pin = out_hbm ? nullptr : (uint8_t*)b->hb_alt.p;
+    v.alt_pin_cap = out_hbm ? 0 : (int64_t)b->hb_alt.cap;
     v.stage_alt_pin = b->staged_kernel ? (uint8_t*)b->hb_alt.p : nullptr; v.stage_alt_cap = b->staged_kernel ? (int64_t)b->hb_alt.cap : 0;
   }
   v.out_valid = 1;
@@ -1922,32 +1857,22 @@ void run_finalize(snf_batch_impl* b) {
     SideStream side(b);
     if (v.wave_path && b->finalize_runs++ > 0) dzero(b, v.big_cnt + 2 * 64 * 16, sizeof(uint32_t) * 64 * 16);   // (the first finalize finds the list empty; a repeated one empties it again)
     if (v.wave_path) {
-      Scope _s(b, "e1w_finalize", 0);
       // one workgroup (= wave) per batch of e1_batch calls, dispatched by the hardware (the kernel strides when there are
       // more calls than the grid covers, workgroups behind the last call return at once)
       int64_t grid = (n_calls_hint + v.e1_batch - 1) / v.e1_batch + 1;
       if (grid > (1 << 20)) grid = 1 << 20;
-      hipLaunchKernelGGL(b->k_e1w, dim3((unsigned)grid), dim3(64), 0, b->cur, v, (int64_t)0);
-      SNF_HIP(hipGetLastError());
+      KERNEL_GRID(e1w_finalize<5>, dim3((unsigned)grid), dim3(64), v, 0, "e1w_finalize", 0, heavy);
     }
-    if (!v.wave_path) LAUNCH_Q(e1_finalize, v, NS, 0);
+    if (!v.wave_path) KERNEL_N(e1_finalize, v, NS, 0, quiet);
     if (v.wave_path && b->have_big_hist && b->hist_big[2] == 0 && b->finalize_runs == 1) b->skipped_big[2] = true;
-    else if (v.wave_path) {
-      Scope _s(b, "x_big_finalize", 0);
-      hipLaunchKernelGGL(x_big<2>, dim3(b->slots_big), dim3(64), 0, b->cur, v, (int64_t)0);
-      SNF_HIP(hipGetLastError());
-    }
+    else if (v.wave_path) KERNEL_GRID(x_big<2>, dim3(b->slots_big), dim3(64), v, 0, "x_big_finalize", 0, heavy);
   }
   const bool fast_alt = v.wave_path && b->fused && NS <= ((int64_t)1 << 22) * 256;
   if (fast_alt)
   {  // E2 sizes -> offsets -> E3 work items in two launches (snf_fused.h) instead of a size kernel, five scans and E3
     const unsigned grid = (unsigned)((NS + 255) / 256);
-    if (b->time_all) { Scope _s(b, "e2a_sizes", 0); hipLaunchKernelGGL(e2a_sizes, dim3(grid), dim3(256), 0, b->cur, v, (int64_t)0); }
-    else hipLaunchKernelGGL(e2a_sizes, dim3(grid), dim3(256), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError());
-    if (b->time_all) { Scope _s(b, "e3b_offsets", 0); hipLaunchKernelGGL(e3b_offsets, dim3(grid), dim3(256), 0, b->cur, v, (int64_t)0); }
-    else hipLaunchKernelGGL(e3b_offsets, dim3(grid), dim3(256), 0, b->cur, v, (int64_t)0);
-    SNF_HIP(hipGetLastError());
+    KERNEL_GRID(e2a_sizes, dim3(grid), dim3(256), v, 0, "e2a_sizes", 0, quiet);
+    KERNEL_GRID(e3b_offsets, dim3(grid), dim3(256), v, 0, "e3b_offsets", 0, quiet);
     SNF_HIP(hipEventRecord(b->ev_e3, b->stream));
     {  // records + read names leave as soon as e1 (side stream), the sv ids / read names (fourth stream) and the ALT
        // lengths (e2a, main) are there - next to the consensus kernels
@@ -1977,13 +1902,13 @@ void run_finalize(snf_batch_impl* b) {
     dsync(b);
     const int64_t nc = b->h_cnt->n_calls;
     dzero(b, v.stripes, sizeof(unsigned long long) * 4 * 64 * 16);
-    LAUNCH(e2_best, v, nc + 1, 0);
+    KERNEL_N(e2_best, v, nc + 1, 0, heavy);
     prim_exscan<uint32_t>(b, v.fN, v.pN, nc + 1, "scan_alt");
     prim_exscan<uint32_t>(b, v.fL, v.pL, nc + 1, "scan_cons");
     prim_exscan<int64_t>(b, v.sz_tab, v.sc_tab, nc + 1, "scan_cons_sizes");
     prim_exscan<int64_t>(b, v.sz_aln, v.sc_aln, nc + 1, "scan_cons_sizes");
     prim_exscan<int64_t>(b, v.sz_rd, v.sc_rd, nc + 1, "scan_cons_sizes");
-    LAUNCH_Q(e3_conslist, v, nc + 1, 0);
+    KERNEL_N(e3_conslist, v, nc + 1, 0, quiet);
     if (v.wave_path) {
       join_fuse_copy(b);
       d2h(b, b->h_cnt, v.cnt, sizeof(Counts));
@@ -2001,7 +1926,7 @@ void run_finalize(snf_batch_impl* b) {
     join_fourth(b);
     enqueue_output_head(b);   // (no positions behind the sort: an empty block)
   }
-  LAUNCH_Q(z1_results, v, tail_threads(v), 0);
+  KERNEL_N(z1_results, v, tail_threads(v), 0, quiet);
   b->res_current = true;
 }
 
@@ -2211,7 +2136,7 @@ bool settle_alt_stage(snf_batch_impl* b) {      // true: ALT bytes were produced
   const Counts& c = *b->h_cnt;
   if (c.n_cls[7] == 0 && c.n_cons_fallback == 0) return false;
   run_alt_fallback(b);     // (they store into the pass's ALT section like the fast kernels)
-  LAUNCH_Q(z1_results, v, tail_threads(v), 0);
+  KERNEL_N(z1_results, v, tail_threads(v), 0, quiet);
   dsync(b);
   return true;
 }
@@ -2514,8 +2439,8 @@ void do_coverage_calls(snf_batch_t* bb, int32_t task_index, int64_t n, const int
     h2d(b, d_t, svtype, (size_t)n * 4); h2d(b, d_p, pos, (size_t)n * 4); h2d(b, d_l, svlen, (size_t)n * 4); h2d(b, d_f, bnd_is_first, (size_t)n);
     h2d(b, q.cov, cov, (size_t)n * 20);
     q.svtype = d_t; q.pos = d_p; q.svlen = d_l; q.bnd_is_first = d_f;
-    LAUNCH(s2_covends, q, 1, n * 13);
-    LAUNCH(s2_covcalls, q, n, (q.hi - q.lo) * 8 + n * 40);
+    KERNEL_N(s2_covends, q, 1, n * 13, heavy);
+    KERNEL_N(s2_covcalls, q, n, (q.hi - q.lo) * 8 + n * 40, heavy);
     int32_t nv[2] = {0, 0};
     d2h(b, cov, q.cov, (size_t)n * 20);
     d2h(b, nv, q.n_valid, 8);
@@ -2696,19 +2621,15 @@ int snf_device_count(void) {
 // handed to the next batch; the pool is bounded, the rest is destroyed as before.
 struct StreamPool {
   std::mutex mu;
-  std::vector<hipStream_t> idle[64], idle_hi[64];   // (idle_hi: streams of the highest priority - the LARGE consensus kernel's)
-  hipStream_t take(int device, bool high = false) {
+  std::vector<hipStream_t> idle[64];
+  hipStream_t take(int device) {
     {
       std::lock_guard<std::mutex> g(mu);
-      auto& v = (high ? idle_hi : idle)[device & 63];
+      auto& v = idle[device & 63];
       if (!v.empty()) { hipStream_t s = v.back(); v.pop_back(); return s; }
     }
     hipStream_t s = nullptr;
-    if (high) {
-      int least = 0, greatest = 0;
-      SNF_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      SNF_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest));
-    } else SNF_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    SNF_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     return s;
   }
   int trim(int device) {      // idle streams of `device` (< 0: all) are destroyed
@@ -2717,8 +2638,7 @@ struct StreamPool {
       std::lock_guard<std::mutex> g(mu);
       for (int d = 0; d < 64; d++) if (device < 0 || (device & 63) == d) {
         for (auto s : idle[d]) gone.push_back({d, s});
-        for (auto s : idle_hi[d]) gone.push_back({d, s});
-        idle[d].clear(); idle_hi[d].clear();
+        idle[d].clear();
       }
     }
     int cur = 0; (void)hipGetDevice(&cur);
@@ -2726,10 +2646,10 @@ struct StreamPool {
     (void)hipSetDevice(cur);
     return (int)gone.size();
   }
-  void give(int device, hipStream_t s, bool high = false) {
+  void give(int device, hipStream_t s) {
     {
       std::lock_guard<std::mutex> g(mu);
-      auto& v = (high ? idle_hi : idle)[device & 63];
+      auto& v = idle[device & 63];
       if (v.size() < 32 && process_knobs().stream_pool) { v.push_back(s); return; }
     }
     (void)hipStreamDestroy(s);
@@ -2738,27 +2658,23 @@ struct StreamPool {
 static StreamPool g_streams;
 
 // The device's CU count and the occupancy of the three resident kernels do not change while the process lives: asked once per
-// (device, instance choice) - hipGetDeviceProperties and the occupancy queries are milliseconds, a task-sized batch is not.
+// device - hipGetDeviceProperties and the occupancy queries are milliseconds, a task-sized batch is not.  d2w_call and e1w_finalize
+// are compiled for five waves per SIMD (the other register budgets were measured and retired: DESIGN.md, "Retired switches");
+// `phase`: the d2w_call instance of the handle that asks first.
 struct DevInfo { int cus, nb_d1w, nb_d2w, nb_e1w; };
-typedef void (*WaveKernel)(const View, int64_t);
-static WaveKernel pick_d2w(int o2, bool phase) {   // waves per SIMD the instance is compiled for x config.phase
-  if (phase) return o2 >= 8 ? d2w_call<8, true> : o2 == 6 ? d2w_call<6, true> : o2 == 5 ? d2w_call<5, true> : d2w_call<4, true>;
-  return o2 >= 8 ? d2w_call<8, false> : o2 == 6 ? d2w_call<6, false> : o2 == 5 ? d2w_call<5, false> : d2w_call<4, false>;
-}
-static DevInfo device_info(int device, int o2, int o1, WaveKernel k_d2w, WaveKernel k_e1w) {
-  typedef std::tuple<int, int, int> Key;
+static DevInfo device_info(int device, bool phase) {
   static std::mutex mu;
-  static std::map<Key, DevInfo> known;
+  static std::map<int, DevInfo> known;
   std::lock_guard<std::mutex> g(mu);
-  auto it = known.find(Key(device, o2, o1));
+  auto it = known.find(device);
   if (it == known.end()) {
     hipDeviceProp_t prop;
     SNF_HIP(hipGetDeviceProperties(&prop, device));
     DevInfo d{prop.multiProcessorCount, 0, 0, 0};
     SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_d1w, d1w_refine<false>, 64, 0));
-    SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_d2w, k_d2w, 64, 0));
-    SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_e1w, k_e1w, 64, 0));
-    it = known.emplace(Key(device, o2, o1), d).first;
+    SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_d2w, (phase ? d2w_call<5, true> : d2w_call<5, false>), 64, 0));
+    SNF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&d.nb_e1w, e1w_finalize<5>, 64, 0));
+    it = known.emplace(device, d).first;
   }
   return it->second;
 }
@@ -2778,7 +2694,7 @@ int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out) {
     b->cfg = *cfg; b->device = device;
     b->stream = g_streams.take(b->device);
     b->stream2 = g_streams.take(b->device);
-    b->stream3 = g_streams.take(b->device, b->k.large_prio);
+    b->stream3 = g_streams.take(b->device);
     b->stream4 = g_streams.take(b->device);
     SNF_HIP(hipEventCreateWithFlags(&b->ev_join4, hipEventDisableTiming));
     SNF_HIP(hipEventCreateWithFlags(&b->ev_e3, hipEventDisableTiming));
@@ -2798,28 +2714,12 @@ int snf_batch_create(const snf_config_t* cfg, int device, snf_batch_t** out) {
        // workgroup a partial second round doubles the kernel time); since the grouped kernels take the small clusters, what the
        // wave-per-cluster kernels walk is a list of a few unequal items per wave, and the dispatcher balances those better than a
        // stride does: same box, two alternations, 0.937 ms per step against 0.955 (x4: 0.934; one in flight 1.35 against 1.37)
-      const int mult = b->k.grid_mult;
-      const int o2 = b->k.occ_d2;
-      const int o1 = b->k.occ_e1;
-      b->k_d2w = pick_d2w(o2, b->cfg.phase != 0);
-      b->k_e1w = o1 == 6 ? e1w_finalize<6> : o1 == 5 ? e1w_finalize<5> : e1w_finalize<4>;  // <8> trips a register-allocation bug of this hipcc
-      const DevInfo di = device_info(b->device, o2, o1, b->k_d2w, b->k_e1w);
+      constexpr int RESIDENT_SETS = 2;
+      const DevInfo di = device_info(b->device, b->cfg.phase != 0);
       const int cus = di.cus;
-      int nb = 0;
-      const int div = b->k.grid_div;
-      if (di.nb_d1w > 0) b->slots_d1w = di.nb_d1w * cus * mult / div;
-      if (di.nb_d2w > 0) b->slots_d2w = di.nb_d2w * cus * mult / div;
-      if (di.nb_e1w > 0) b->slots_e1w = di.nb_e1w * cus * mult / div;
-      // The consensus kernels take one call per workgroup from the hardware dispatcher: measured alone on config 1, resident
-      // (persistent) grids were slower whether they strode statically (0.315 / 0.419 ms SMALL / LARGE, a tail of unequal calls)
-      // or claimed calls from a counter (0.498 / 0.382 ms) - against 0.286 / 0.306 ms for plain grids.  SNF_CONS_GRID_MULT=k
-      // caps the grid at k x the resident workgroups (the kernels stride) for experiments.
-      b->slots_cons_s = b->slots_cons_l = 1 << 22;
-      if (const int m = b->k.cons_grid_mult; m != KNOB_UNSET) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (K_CONS_SMALL(5)), 256, 0) == hipSuccess && nb > 0) b->slots_cons_s = nb * cus * m;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (K_CONS_LARGE), 256, 0) == hipSuccess && nb > 0) b->slots_cons_l = nb * cus * m;
-      }
-      b->slots_cons_s1 = b->k.cons_small_grid;
+      if (di.nb_d1w > 0) b->slots_d1w = di.nb_d1w * cus * RESIDENT_SETS;
+      if (di.nb_d2w > 0) b->slots_d2w = di.nb_d2w * cus * RESIDENT_SETS;
+      if (di.nb_e1w > 0) b->slots_e1w = di.nb_e1w * cus * RESIDENT_SETS;
       b->slots_big = ((32 * cus) / 64) * 64; if (b->slots_big < 64) b->slots_big = 64;   // x_big: a multiple of its 64 stripes
       if (b->k.prof) fprintf(stderr, "[SNF_PROF] resident workgroups: d1w %d d2w %d e1w %d (CUs %d)\n", b->slots_d1w, b->slots_d2w, b->slots_e1w, cus);
     }
@@ -2894,7 +2794,7 @@ void snf_batch_destroy(snf_batch_t* bb) {
   b->ext_ranges.clear();
   if (b->stream) g_streams.give(b->device, b->stream);   // (synchronised above)
   if (b->stream2) g_streams.give(b->device, b->stream2);   // (synchronised above)
-  if (b->stream3) g_streams.give(b->device, b->stream3, b->k.large_prio);   // (synchronised above)
+  if (b->stream3) g_streams.give(b->device, b->stream3);   // (synchronised above)
   if (b->stream4) g_streams.give(b->device, b->stream4);   // (synchronised above)
   if (b->ev_join4) (void)hipEventDestroy(b->ev_join4);
   delete b;
@@ -3021,7 +2921,7 @@ int snf_batch_block_coverage(snf_batch_t* bb, int32_t task_index, int32_t binsiz
     q.nm_start = b->v.nm_start; q.nm_end = b->v.nm_end; q.nm_lo = b->h_nm_off[(size_t)task_index]; q.nm_hi = b->h_nm_off[(size_t)task_index + 1];
     q.exact = b->h_cov_exact.empty() ? 0 : b->h_cov_exact[(size_t)task_index];
     q.out = dalloc_own<int32_t>(b, (size_t)n_bins);
-    LAUNCH(s1_blockcov, q, n_bins, (q.hi - q.lo) * 8 + n_bins * 4);
+    KERNEL_N(s1_blockcov, q, n_bins, (q.hi - q.lo) * 8 + n_bins * 4, heavy);
     d2h(b, out, q.out, (size_t)n_bins * 4);
     dsync(b);
     dfree_one(b, q.out);

@@ -187,7 +187,6 @@ struct View {
   // dev_min_leads_cluster >= 2 (cluster.py:262) - 80 % of the leads of a 30x genome - and is dropped in front of the sort.
   // Two bits per cell ("seen", "seen twice"); the words a pass touched are cleared again by the pass itself.
   int32_t prefilter;          // 1: on
-  int32_t pf_spread;          // 1: neighbouring cells are spread over the L2 channels (pf_slot); SNF_PF_SPREAD=0 keeps them adjacent
   uint32_t* pf_bm;            // [pf_words] 16 cells per word
   const int64_t* t_cell_off;  // [T+1] first cell of task t (cells of a task: SNF_NTYPES x (contig_len / binsize + 1))
   uint64_t* pf_key;           // [N] sort key per input lead (uint32_t when key32), written by a1_keys
