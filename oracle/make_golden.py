@@ -257,6 +257,29 @@ def main_consensus_class_edges():
         f.write(json.dumps(doc, sort_keys=True, separators=(",", ":")).encode())
 
 
+def main_consensus_thresholds():
+    """Golden vectors for the directed problems ON the decision thresholds of the consensus (tests/consensus_cases.py): the reference's own
+    consensus.novel_from_reads.  The reads come from the builder and are not stored: per problem the hash of its input, klen, skip and
+    the reference's result."""
+    import consensus_cases as cc
+    import ref_harness as rh
+    ref = rh.load_reference()
+
+    class L:
+        def __init__(self, seq):
+            self.seq = seq
+
+    out = []
+    for p in cc.cases():
+        exp = ref.consensus.novel_from_reads(L(p["best"]), [L(o) for o in p["others"]], klen=p["klen"], skip=p["skip"], skip_repetitive=p["skip"])
+        out.append(dict(name=p["name"], input_sha=cc.problem_sha(p), klen=p["klen"], skip=p["skip"], expected=exp))
+    doc = dict(case="consensus_thresholds", n=len(out), problems=out)
+    with gzip.GzipFile(os.path.join(ROOT, "tests", "golden", "consensus_thresholds.json.gz"), "wb", mtime=0) as f:
+        f.write(json.dumps(doc, sort_keys=True, separators=(",", ":")).encode())
+    changed = sum(1 for p, d in zip(cc.cases(), out) if d["expected"] != p["best"])
+    print(f"consensus_thresholds: {len(out)} problems, {changed} with a consensus that differs from the best read")
+
+
 def main_combine_task(names=None):
     """Goldens for the CombineTask.execute driver: inputs (SNF blocks per sample) and the combined calls it emits."""
     import cases
@@ -520,7 +543,7 @@ if __name__ == "__main__":
     # python oracle/make_golden.py                 -> every fixture family
     # python oracle/make_golden.py vcf sample      -> only these families
     # python oracle/make_golden.py main fuzz_4_2   -> single cases of the `main` / `combine` families
-    FAMILIES = dict(main=main, clusters=main_clusters, regenotype=main_regenotype, combine=main_combine, consensus=main_consensus, consensus_long=main_consensus_long, consensus_class_edges=main_consensus_class_edges, combine_task=main_combine_task,
+    FAMILIES = dict(main=main, clusters=main_clusters, regenotype=main_regenotype, combine=main_combine, consensus=main_consensus, consensus_long=main_consensus_long, consensus_class_edges=main_consensus_class_edges, consensus_thresholds=main_consensus_thresholds, combine_task=main_combine_task,
                     bam=main_bam_fixtures, extract=main_extract, snf=main_snf, vcf=main_vcf, sample=main_sample, genotype=main_genotype, population=main_population, genotype_vcf=main_genotype_vcf,
                     genotype_edges=main_genotype_edges)
     argv = sys.argv[1:]
