@@ -684,7 +684,13 @@ typedef struct snf_extract_config {
 } snf_extract_config_t;
 
 typedef struct snf_extract_input {
-  const uint8_t* records;   /* inflated BAM alignment records back to back, each starting with its block_size field */
+  const uint8_t* records;   /* inflated BAM alignment records back to back, each starting with its block_size field.
+                               The effective CIGAR (SAM/BAM spec 4.2.2, CIGARs of more than 65 535 operations): a record's CIGAR is
+                               the array of its first CG tag when ref_id >= 0 and pos >= 0, n_cigar_op >= 1, inline operation 0
+                               is S of exactly l_seq (0S with l_seq == 0 included), the first tag named CG has type B with
+                               sub-type I, and its count is >= n_cigar_op and >= 1; in every other case it is the inline one.
+                               A qualifying array that runs past the end of its record fails the run (malformed auxiliary
+                               field).  The tag takes no further part: the tag walk skips it like any other array. */
   int64_t records_len;
   const int64_t* rec_off;   /* n_records + 1 byte offsets into `records` */
   int64_t n_records;        /* file order; records of other contigs / unmapped records are skipped */

@@ -81,7 +81,8 @@ struct ExView {
   int64_t *c_acc, *c_leads, *c_seq;
   double* c_nm;                       // per record: its NM ratio if it counts for average_regional_nm (accepted, NM tag, advanced tags), else +0.0
   int64_t* c_ps; uint8_t* c_psf;      // per record: its PS tag and whether it counts (accepted, tag present) - what the host ranks
-  unsigned long long* tot;            // [0] first error (= err), [1..3] reads, leads, sequence bytes, [4] NM summands: one copy to the host
+  unsigned long long* tot;            // [0] first error (= err), [1..3] reads, leads, sequence bytes, [4] NM summands, [5] noted placeholders: one copy to the host
+  uint32_t* cg_list;                  // wave form: the placeholder-shaped records the counting pass noted (tot[5] of them, any order)
   const int64_t *read_idx, *lead_off, *seq_off;
   const int64_t* ps_val; const int32_t* ps_rank; int32_t n_ps, ps_null_rank;
   // lead columns
@@ -482,14 +483,62 @@ template <bool WAVE> SNF_HD void x_parse_tags(const uint8_t* A, int32_t aux_len,
   t.bad = bad;
 }
 
+// ---- the effective CIGAR of a placeholder record (SAM/BAM spec 4.2.2; the rule: include/sniffles_amd.h, snf_extract input) -------
+// A record of more than 65 535 operations carries `kSmN` inline (k = l_seq, m = its reference span) and the operations in a
+// CG:B,I tag.  Only a record whose first inline operation is S of l_seq comes here.  The FIRST tag named CG decides: type B,
+// sub-type I, a count >= the inline count and >= 1.  1: *rel = offset of the array inside the auxiliary region (any byte offset),
+// *cnt = its operations; 0: the inline CIGAR stays (no such tag, another type, or a tag in front of it that cannot be walked);
+// -1: the array runs past the end of the record.  `A`: the auxiliary region (LDS copy or blob), walked like x_parse_tags does.
+template <bool WAVE> SNF_HD int x_find_cg(const uint8_t* A, int32_t aux_len, int n_inl, int lane, int32_t* rel, int32_t* cnt) {
+  int64_t p = 0;
+  while (p + 3 <= aux_len) {
+    const uint64_t w = x_uni64<WAVE>(x_ld8(A + p));
+    const uint8_t ty = (uint8_t)(w >> 16), sub = (uint8_t)(w >> 24);
+    const bool cg = (uint16_t)w == (uint16_t)('C' | ('G' << 8));
+    p += 3;
+    switch (ty) {
+      case 'A': case 'c': case 'C': p += 1; break;
+      case 's': case 'S': p += 2; break;
+      case 'i': case 'I': case 'f': p += 4; break;
+      case 'Z': case 'H': {
+        const int64_t z = x_find_nul<WAVE>(A, p, aux_len, lane);
+        if (z < 0) return 0;
+        p = z + 1;
+        break; }
+      case 'B': {
+        const int64_t n = (int32_t)(uint32_t)(w >> 32);
+        const int sz = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+        if (!sz || n < 0 || p + 5 > aux_len) return 0;
+        if (cg) {
+          if (sub != 'I' || n < n_inl || n < 1) return 0;
+          if (p + 5 + 4 * n > aux_len) return -1;
+          *rel = (int32_t)(p + 5); *cnt = (int32_t)n;
+          return 1;
+        }
+        p += 5 + n * sz;
+        break; }
+      default: return 0;
+    }
+    if (cg) return 0;
+  }
+  return 0;
+}
+
 // ---- one alignment record ----------------------------------------------------------------------------------------
 #ifndef X_AHEAD
 #define X_AHEAD 2      /* measured: 2 = 3 = 4 steps ahead (0.108 / 0.111 / 0.114 ms per counting pass); the walk is not what a pass waits for */
 #endif
 #define XAUXCAP 1024   // bytes of a record's auxiliary region (counting pass) / of its SA string (emit pass) the wave form keeps in LDS;
                        // a longer one (base-modification arrays ...) is parsed where it lies in the blob
-template <bool WAVE, bool EMIT>
-SNF_HD void extract_record(int64_t rec, const ExView& v, Seg* segs, uint8_t* ord, uint8_t* auxl, int32_t* sab) {
+// MODE 0: the record as the main kernels take it, with its inline CIGAR.  A placeholder-shaped record (S of l_seq first) does not
+// belong there: the wave form's counting pass only notes it in `cg_list` and returns - a launch of their own takes the noted
+// records (x_wave_cg), so that the ordinary kernels' registers and code stay what ordinary records need -, the thread form
+// resolves it on the spot.  MODE 1: a noted record that keeps its inline CIGAR after all; MODE 2: its CIGAR is the array of its CG
+// tag (cg_ops, cg_n).  The wave form marks what MODE 1 / 2 accepted with accept == 2, which the main emit kernel skips.
+template <bool WAVE, bool EMIT, int MODE = 0>
+SNF_HD void extract_record(int64_t rec, const ExView& v, Seg* segs, uint8_t* ord, uint8_t* auxl, int32_t* sab, const uint8_t* cg_ops = nullptr, int cg_n = 0) {
+  constexpr bool CG = MODE == 2;
+  constexpr uint8_t ACCEPT = (WAVE && MODE != 0) ? 2 : 1;
   const int lane = x_lane<WAVE>();
   const int W = WAVE ? 64 : 1;
   const snf_extract_config_t& cfg = v.cfg;
@@ -509,16 +558,19 @@ SNF_HD void extract_record(int64_t rec, const ExView& v, Seg* segs, uint8_t* ord
   else if (lane == 0) { S.accept = 0; S.n_leads = 0; S.seq_bytes = 0; S.has_nm = 0; S.has_ps = 0; S.nm = -1.0; S.sa_rel = -1; S.sa_len = 0; S.hp = 0; S.ps = 0; S.nm_tag = 0; S.ref_end = 0; }
   uint32_t hd[6];
   x_header<WAVE>(R, lane, hd);
-  if (EMIT) { if (!sv.accept) return; }
+  if (EMIT) { if (sv.accept != ACCEPT) return; }
   const int32_t block_size = (int32_t)hd[0];
   const int32_t ref_id = (int32_t)hd[1], pos = (int32_t)hd[2];
   const int l_name = (int)(hd[3] & 0xffu), mapq = (int)((hd[3] >> 8) & 0xffu);
-  const int n_cig = (int)(hd[4] & 0xffffu), flag = (int)(hd[4] >> 16);
+  const int n_inl = (int)(hd[4] & 0xffffu), flag = (int)(hd[4] >> 16);   // the inline operation count (16 bits)
   const int32_t l_seq = (int32_t)hd[5];
   if (ref_id != v.region_ref_id || (flag & 0x4)) return;
-  if (n_cig == 0) { if (!EMIT && lane == 0) x_error(v, rec, XE_NOCIGAR); return; }
-  const uint8_t* cig = R + 36 + l_name;
-  const uint8_t* seq = cig + 4 * (int64_t)n_cig;
+  if (n_inl == 0) { if (!EMIT && lane == 0) x_error(v, rec, XE_NOCIGAR); return; }
+  // the CIGAR that is walked: the inline one, or the array of the CG tag (resolved below, before any operation is looked at);
+  // the sequence lies behind the INLINE operations either way
+  const uint8_t* cig = CG ? cg_ops : R + 36 + l_name;
+  const int n_cig = CG ? cg_n : n_inl;
+  const uint8_t* seq = R + 36 + l_name + 4 * (int64_t)n_inl;
   const int64_t aux0 = (int64_t)(seq - v.blob) + (l_seq + 1) / 2 + l_seq, aux1 = roff + 4 + block_size;
   const int32_t aux_len = (int32_t)(aux1 - aux0);
   // ---- everything the record needs next is requested here, in one round trip:
@@ -558,6 +610,27 @@ SNF_HD void extract_record(int64_t rec, const ExView& v, Seg* segs, uint8_t* ord
   if (base0 < base1) x_load_ops<WAVE>(cig, n_cig, base0, lane, cur);
 #pragma unroll
   for (int d = 0; d + 1 < XD; d++) if (base0 + (d + 1) * STEP < base1) x_load_ops<WAVE>(cig, n_cig, base0 + (d + 1) * STEP, lane, nx[d]);
+  // ---- the effective CIGAR.  An ordinary record pays one compare on operation 0, which lane 0 holds (and none in the wave form's
+  // emit pass: what the counting pass noted has accept == 2 and left above)
+  if (MODE == 0 && !(WAVE && EMIT)) {
+    uint32_t op0;
+#if XDEV
+    if (WAVE) op0 = (uint32_t)__builtin_amdgcn_readlane((int)cw, 0); else
+#endif
+    op0 = ld_u32(cig);
+    if (op0 == (((uint32_t)l_seq << 4) | 4u) && (uint32_t)l_seq < (1u << 28) && ref_id >= 0 && pos >= 0) {
+#if XDEV
+      if (WAVE) {
+        if (lane == 0) v.cg_list[atomicAdd(&v.tot[5], 1ull)] = (uint32_t)rec;
+        return;
+      }
+#endif
+      int32_t cg_rel = 0, cg_cnt = 0;
+      const int found = x_find_cg<WAVE>(A, aux_len, n_inl, lane, &cg_rel, &cg_cnt);
+      if (found < 0) { if (!EMIT && lane == 0) x_error(v, rec, XE_AUX); return; }
+      if (found > 0) { extract_record<WAVE, EMIT, 2>(rec, v, segs, ord, auxl, sab, v.blob + aux0 + cg_rel, cg_cnt); return; }
+    }
+  }
   // pysam getQueryStart / getQueryEnd
   int32_t q0 = 0, q1 = l_seq; bool clip_bad = false;
   uint32_t c_first, c_last;
@@ -980,7 +1053,7 @@ SNF_HD void extract_record(int64_t rec, const ExView& v, Seg* segs, uint8_t* ord
   XT_ADD(2, xt_sa0)
   if (!EMIT) {
     if (lane == 0 && lead_k >= 0) {
-      S.accept = 1; S.n_leads = lead_k; S.seq_bytes = seqb; S.has_nm = has_nm; S.has_ps = has_ps; S.nm = nm; S.sa_rel = sa_rel; S.sa_len = sa_len;
+      S.accept = ACCEPT; S.n_leads = lead_k; S.seq_bytes = seqb; S.has_nm = has_nm; S.has_ps = has_ps; S.nm = nm; S.sa_rel = sa_rel; S.sa_len = sa_len;
       S.hp = (uint8_t)hp; S.ps = ps; S.nm_tag = nm_tag; S.ref_end = ref_end;
       S.walk_lo = w_lo; S.walk_hi = w_hi; S.walk_pr = w_pr; S.walk_pf = w_pf;
     }
@@ -1044,6 +1117,31 @@ __global__ void __launch_bounds__(64, MINW) x_wave(const ExView v, int64_t n) {
   // what a pass over a small table ended with: 40 % of its span with a few hundred waves in flight)
   for (int64_t w = (int64_t)blockIdx.x; w < n; w += (int64_t)gridDim.x)
     extract_record<true, EMIT>((int64_t)v.order[w], v, segs, ord, auxl, sab);
+}
+// The placeholder-shaped records the counting pass noted, one wave each: the record's CG tag is looked for where the record lies
+// (x_find_cg walks every tag in front of it, one 8-byte read per tag) and the record goes through extract_record with the tag's
+// array as its CIGAR, or with its inline one where no tag qualifies.  Launched only when the list is not empty.
+template <bool EMIT>
+__global__ void __launch_bounds__(64, 4) x_wave_cg(const ExView v, int64_t n) {
+  __shared__ Seg segs[XMAXSEG];
+  __shared__ uint8_t ord[XMAXSEG];
+  __shared__ alignas(16) uint8_t auxl[XAUXCAP + 16];
+  __shared__ int32_t sab[2 * XMAXSEG];
+  const int lane = x_lane<true>();
+  for (int64_t w = (int64_t)blockIdx.x; w < n; w += (int64_t)gridDim.x) {
+    const int64_t rec = (int64_t)v.cg_list[w];
+    const int64_t roff = v.rec_off[rec];
+    uint32_t hd[6];
+    x_header<true>(v.blob + roff, lane, hd);
+    const int n_inl = (int)(hd[4] & 0xffffu); const int32_t l_seq = (int32_t)hd[5];
+    const int64_t aux0 = roff + 36 + (int64_t)(hd[3] & 0xffu) + 4 * (int64_t)n_inl + (l_seq + 1) / 2 + l_seq, aux1 = roff + 4 + (int32_t)hd[0];
+    int32_t cg_rel = 0, cg_cnt = 0;
+    const int found = x_find_cg<true>(v.blob + aux0, (int32_t)(aux1 - aux0), n_inl, lane, &cg_rel, &cg_cnt);
+    if (found < 0) { if (!EMIT && lane == 0) x_error(v, rec, XE_AUX); }
+    else if (found > 0)
+      extract_record<true, EMIT, 2>(rec, v, segs, ord, auxl, sab, v.blob + aux0 + (int32_t)x_uni<true>((uint32_t)cg_rel), (int)x_uni<true>((uint32_t)cg_cnt));
+    else extract_record<true, EMIT, 1>(rec, v, segs, ord, auxl, sab);
+  }
 }
 // average_regional_nm needs the reads' NM ratios summed in BAM order (leadprov.py:533-534, 577): sequential fp64 adds.
 // x_prep has laid the summands out densely (a record that does not count as +0.0).  Adding a zero is the identity here - the sum starts
@@ -1130,7 +1228,7 @@ struct snf_extract {
   int device = 0;
   std::vector<void*> dev;        // device allocations of the current input / run
   XSlab run_a, run_b;            // what a run needs before / after the scans: two grow-only device blocks carved into arrays
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev_prep = nullptr;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t ev_prep = nullptr;      // [4], [5]: around the placeholders' counting launch
   size_t scan_tmp = 0; int64_t scan_n = -1;
   ExView v{};
   int64_t n_records = 0, blob_len = 0;
@@ -1211,17 +1309,31 @@ void x_take_input(snf_extract* x, const snf_extract_input_t* in, const int64_t* 
   v.qname_rank = x_up(x->dev, in->qname_rank, (size_t)in->n_records);
   v.ctg_hash = x_up(x->dev, in->contig_hash, (size_t)in->n_contigs);
   v.ctg_rank = x_up(x->dev, in->contig_rank, (size_t)in->n_contigs);
-  {  // dispatch order of the wave form: counting sort of the records by CIGAR length, longest first; records of other contigs last
+  {  // dispatch order of the wave form: counting sort of the records by CIGAR length, longest first; records of other contigs last.
+     // A record that may be the placeholder of a CIGAR of more than 65 535 operations goes in front of them all, by falling bound.
+     // Only the fixed fields are at hand for attached input, so both inputs use what those give: an inline count of 1 or 2 (what
+     // a writer leaves of `kSmN`) and an auxiliary region that could hold a CG array of more than 65 535 operations (8 bytes of tag
+     // header, 4 per operation).  The bound is the region's length over 4; a record it ranks too high merely starts early.
     const int64_t n = in->n_records;
-    std::vector<uint32_t> cnt(65538, 0), ord((size_t)(n ? n : 1));
-    auto key = [&](int64_t i) -> uint32_t {
+    std::vector<uint32_t> cnt(65539, 0), ord((size_t)(n ? n : 1));
+    auto cg_bound = [&](int64_t i) -> int64_t {
+      const uint8_t* R = head(i);
+      int32_t bs, l_seq; uint16_t nc; memcpy(&bs, R, 4); memcpy(&nc, R + 16, 2); memcpy(&l_seq, R + 20, 4);
+      if (nc < 1 || nc > 2) return 0;
+      const int64_t aux = (int64_t)bs + 4 - (36 + (int64_t)R[12] + 4 * (int64_t)nc + ((int64_t)l_seq + 1) / 2 + l_seq);
+      return (aux - 8) / 4 > 65535 ? (aux - 8) / 4 : 0;
+    };
+    auto key = [&](int64_t i) -> uint32_t {      // 0: the placeholder candidates; 1..65536: inline counts 65535..0; 65537: other contigs
       const uint8_t* R = head(i);
       int32_t rid; uint16_t nc; memcpy(&rid, R + 4, 4); memcpy(&nc, R + 16, 2);
-      return rid == in->region_ref_id ? 65535u - nc : 65536u;
+      if (rid != in->region_ref_id) return 65537u;
+      return cg_bound(i) ? 0u : 65536u - nc;
     };
     for (int64_t i = 0; i < n; i++) cnt[key(i) + 1]++;
     for (size_t k = 1; k < cnt.size(); k++) cnt[k] += cnt[k - 1];
+    const size_t n_front = cnt[1];
     for (int64_t i = 0; i < n; i++) ord[cnt[key(i)]++] = (uint32_t)i;
+    std::stable_sort(ord.begin(), ord.begin() + n_front, [&](uint32_t a, uint32_t b) { return cg_bound(a) > cg_bound(b); });
     v.order = x_up(x->dev, ord.data(), (size_t)(n ? n : 1));
   }
   v.n_contigs = in->n_contigs; v.n_records = in->n_records;
@@ -1306,6 +1418,7 @@ int do_run(snf_extract* x) {
     v.c_acc = s.take<int64_t>(N1); v.c_leads = s.take<int64_t>(N1); v.c_seq = s.take<int64_t>(N1);
     v.c_ps = s.take<int64_t>((size_t)n); v.c_psf = s.take<uint8_t>((size_t)n); v.c_nm = s.take<double>((size_t)n);
     v.nm_out = s.take<double>(2);
+    v.cg_list = s.take<uint32_t>((size_t)n);
     d_read_idx = s.take<int64_t>(N1); d_lead_off = s.take<int64_t>(N1); d_seq_off = s.take<int64_t>(N1);
     d_tmp = s.take<uint8_t>(x->scan_tmp);
 #ifdef SNF_XTRACE
@@ -1315,7 +1428,7 @@ int do_run(snf_extract* x) {
   x->run_a.measure(); carve_a(x->run_a); x->run_a.reserve(); carve_a(x->run_a);
   v.read_idx = d_read_idx; v.lead_off = d_lead_off; v.seq_off = d_seq_off;
   const unsigned long long none = ~0ull;
-  { const unsigned long long init[8] = {none, 0, 0, 0, 0, 0, 0, 0}; x_h2d(v.tot, init, 64); }      // [0] first error, [4] NM summands (x_prep)
+  { const unsigned long long init[8] = {none, 0, 0, 0, 0, 0, 0, 0}; x_h2d(v.tot, init, 64); }      // [0] first error, [4] NM summands (x_prep), [5] noted placeholders
 #ifdef SNF_XTRACE
   SNF_HIP(hipMemset(v.xtrace, 0, (size_t)(n ? n : 1) * 16));
   v.xtrace_emit = k.xtrace_emit;
@@ -1334,21 +1447,36 @@ int do_run(snf_extract* x) {
     else x_launch_wave<false>(waves, grid_w, v, n);
   }
   SNF_HIP(hipEventRecord(e1, 0));
-  hipLaunchKernelGGL(x_prep, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, 0, v, n + 1);
   if (!x->side) SNF_HIP(hipStreamCreateWithFlags(&x->side, hipStreamNonBlocking));
   if (!x->ev_prep) SNF_HIP(hipEventCreateWithFlags(&x->ev_prep, hipEventDisableTiming));
-  SNF_HIP(hipEventRecord(x->ev_prep, 0));
-  SNF_HIP(hipStreamWaitEvent(x->side, x->ev_prep, 0));      // the serial sum runs beside the scans, the host round trip and the emit pass
-  hipLaunchKernelGGL(x_nmsum, dim3(1), dim3(64), 0, x->side, v, n);
-  {
+  unsigned long long tot[8] = {none, 0, 0, 0, 0, 0, 0, 0}; double nmv[2] = {0, 0};
+  auto sums = [&]() {      // the summaries -> scan inputs, the NM sum, the three scans, the totals: one copy to the host
+    hipLaunchKernelGGL(x_prep, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, 0, v, n + 1);
+    SNF_HIP(hipEventRecord(x->ev_prep, 0));
+    SNF_HIP(hipStreamWaitEvent(x->side, x->ev_prep, 0));      // the serial sum runs beside the scans, the host round trip and the emit pass
+    hipLaunchKernelGGL(x_nmsum, dim3(1), dim3(64), 0, x->side, v, n);
     size_t need = x->scan_tmp;
     SNF_HIP(rocprim::exclusive_scan(d_tmp, need, (const int64_t*)v.c_acc, d_read_idx, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
     SNF_HIP(rocprim::exclusive_scan(d_tmp, need, (const int64_t*)v.c_leads, d_lead_off, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
     SNF_HIP(rocprim::exclusive_scan(d_tmp, need, (const int64_t*)v.c_seq, d_seq_off, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+    hipLaunchKernelGGL(x_totals, dim3(1), dim3(64), 0, 0, v, (int64_t)1);
+    x_d2h(tot, v.tot, 64);
+  };
+  sums();
+  // placeholder-shaped records (CIGARs of more than 65 535 operations, CG tag) that the wave form noted: a launch of their own, and
+  // the sums once more over all summaries (rare; an ordinary file never comes here)
+  const int64_t n_cg = thread_form ? 0 : (int64_t)tot[5];
+  float ms_cg = 0;
+  if (n_cg) {
+    SNF_HIP(hipStreamSynchronize(x->side));      // the first NM sum is through with c_nm
+    const unsigned long long zero = 0;
+    x_h2d(v.tot + 4, &zero, 8);                  // x_prep counts the NM summands again
+    const unsigned grid_cg = (unsigned)std::min<int64_t>(n_cg, grid_cap);
+    SNF_HIP(hipEventRecord(x->ev[4], 0));
+    hipLaunchKernelGGL((x_wave_cg<false>), dim3(grid_cg), dim3(64), 0, 0, v, n_cg);
+    SNF_HIP(hipEventRecord(x->ev[5], 0));
+    sums();
   }
-  hipLaunchKernelGGL(x_totals, dim3(1), dim3(64), 0, 0, v, (int64_t)1);
-  unsigned long long tot[8] = {none, 0, 0, 0, 0, 0, 0, 0}; double nmv[2] = {0, 0};
-  x_d2h(tot, v.tot, 64);
   const unsigned long long err = tot[0]; const int64_t n_reads = (int64_t)tot[1], n_leads = (int64_t)tot[2], n_seq = (int64_t)tot[3];
   if (err != none) {
     const int code = (int)(err & 0xff);
@@ -1388,11 +1516,13 @@ int do_run(snf_extract* x) {
   if (n) {
     if (thread_form) hipLaunchKernelGGL(x_emit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, v, n);
     else x_launch_wave<true>(waves, grid_w, v, n);
+    if (n_cg) hipLaunchKernelGGL((x_wave_cg<true>), dim3((unsigned)std::min<int64_t>(n_cg, grid_cap)), dim3(64), 0, 0, v, n_cg);
   }
   SNF_HIP(hipEventRecord(e3, 0));
   SNF_HIP(hipStreamSynchronize(x->side));
   SNF_HIP(hipDeviceSynchronize());
   SNF_HIP(hipEventElapsedTime(&ms_count, e0, e1)); SNF_HIP(hipEventElapsedTime(&ms_emit, e2, e3));
+  if (n_cg) { SNF_HIP(hipEventElapsedTime(&ms_cg, x->ev[4], x->ev[5])); ms_count += ms_cg; }      // the counting pass is both launches
   x_d2h(nmv, v.nm_out, 8); nmv[1] = (double)tot[4];
 #ifdef SNF_XTRACE
   if (const char* path = k.xtrace_out.empty() ? nullptr : k.xtrace_out.c_str()) {

@@ -50,9 +50,30 @@ def cigar_string(ops) -> str:
     return "".join(f"{ln}{OPS[op]}" for op, ln in ops)
 
 
-def make_record(ref_id, pos, mapq, flag, qname, ops, seq_codes, tags: bytes) -> bytes:
+def cg_tag(ops) -> bytes:
+    """The CG:B,I tag that carries a CIGAR (SAM/BAM spec 4.2.2)."""
+    return b"CGBI" + struct.pack(f"<i{len(ops)}I", len(ops), *[(ln << 4) | op for op, ln in ops])
+
+
+def make_record(ref_id, pos, mapq, flag, qname, ops, seq_codes, tags, cg=None, cg_at=None) -> bytes:
+    """One raw alignment record.  A CIGAR of more than 65 535 operations does not fit the 16-bit count and is written the way htslib
+    writes it: `kSmN` inline (k = l_seq, m = the reference span of the real CIGAR) and the operations in a CG:B,I tag behind the
+    caller's tags.  `cg=True` forces that form for any operation count.  `cg_at` places the tag among the caller's tags instead: `tags`
+    is then a list of whole tags and CG becomes element `cg_at` of it."""
     l_seq = int(len(seq_codes))
     name = qname.encode("ascii") + b"\0"
+    if cg is None:
+        cg = len(ops) > 65535
+    if not isinstance(tags, (bytes, bytearray)):
+        tags = list(tags)
+        if cg:
+            tags.insert(len(tags) if cg_at is None else cg_at, cg_tag(ops))
+        tags = b"".join(tags)
+    elif cg:
+        assert cg_at is None, "cg_at needs the tags as a list"
+        tags = bytes(tags) + cg_tag(ops)
+    if cg:
+        ops = [(S, l_seq), (N, sum(ln for op, ln in ops if op in (M, D, N, EQ, X)))]
     cig = struct.pack(f"<{len(ops)}I", *[(ln << 4) | op for op, ln in ops])
     sc = np.asarray(seq_codes, np.uint8)
     if l_seq & 1:
