@@ -638,6 +638,76 @@ int snf_combine_call_groups(const snf_group_call_config_t* cfg, int device, int6
                             snf_group_out_t* out, uint8_t* member_chosen, double* member_pos_mean);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * Force calling (--genotype-vcf): the match of GenotypeTask.execute (src/sniffles/parallel.py:300-369) - every target SV of
+ * the input VCF takes the closest candidate of its type within the merge gates.  Candidates in candidate order, targets in
+ * input order; svtype: SNF_* codes (a target whose type is not one of sv.TYPES: any other value, e.g. -1; candidates of
+ * the SINGLE_* types take no part); positions >= 0.  Per target t:
+ *   visible in bin b0 = t.pos / 5000, in b0 - 1 iff t.pos % 5000 < 500, in b0 + 1 iff t.pos % 5000 > 4500;
+ *   candidate c sees t iff the types are equal and c.pos / 5000 is one of those bins (a bin rule, not a distance rule);
+ *   BND: dist = |t.pos - c.pos|, accepted iff dist <= cluster_merge_bnd and the mate contigs are equal (the caller maps the
+ *        target's mate name into the candidates' numbering; a name they do not know gets a value no candidate has);
+ *   else: dist = |t.pos - c.pos| + ||t.svlen| - |c.svlen||, minlen = min(|t.svlen|, |c.svlen|), accepted iff minlen > 0,
+ *        (double)dist <= (double)combine_match * sqrt((double)minlen) and dist <= combine_match_max;
+ *   out_best[t] = the accepted candidate of smallest dist, the earliest in candidate order among equals (-1: none),
+ *   out_dist[t] = its dist (0 without a match).
+ * On the device: a (type, bin) key per candidate, a stable radix sort, one wave per target (form 0) or one thread per target
+ * (form 1) over the sorted bins; max_grid > 0 caps the workgroups of the match (the kernels stride), <= 0: no cap.  Both are
+ * test hooks: the result does not depend on them.  Staged through a persistent per-device arena like the combine entry points.
+ */
+typedef struct snf_gtmatch {
+  int64_t n_candidates;
+  const int32_t* c_svtype;
+  const int32_t* c_pos;
+  const int32_t* c_svlen;
+  const int32_t* c_mate_contig;
+  int64_t n_targets;
+  const int32_t* t_svtype;
+  const int32_t* t_pos;
+  const int32_t* t_svlen;
+  const int32_t* t_mate_contig;
+  int32_t* out_best;           /* n_targets */
+  int32_t* out_dist;           /* n_targets */
+} snf_gtmatch_t;
+
+int snf_genotype_match_batch(const snf_config_t* cfg, int device, const snf_gtmatch_t* in, int32_t max_grid, int32_t form);
+/* measurement: kernel time (HIP events around keys + sort + match) of the last snf_genotype_match_batch on `device`;
+ * stats4: [0] targets, [1] candidates, [2] workgroups of the match, [3] bytes staged host -> HBM */
+int snf_genotype_match_last_stats(int device, double* kernel_ms, int64_t* stats4);
+
+/* GenotypeTask.execute behind the candidates (parallel.py:326-366) for a task whose finalized candidates are still in HBM:
+ * call after snf_batch_set_output(SNF_OUT_CANDIDATES | SNF_OUT_DEVICE) + snf_batch_pass (or call_candidates + finalize).
+ * Nothing of the candidates is downloaded.  On the device:
+ *   match     the rule above against the task's candidates where they lie (mate_contig: the task's contig numbering);
+ *   coverage  postprocessing.coverage for the targets - the device code and the rules of snf_batch_coverage_calls: cov is
+ *             5 ints per target, in / out, a sample outside the vector keeps its input value (SNF_NONE_I32: unset), and
+ *             *status = 1 when a BND comes before any other target (the targets from there on are left untouched);
+ *   genotype  out_gt: 8 ints per target - a, b, GQ, DR, DV, hp (-1 None), ps (-1 None, -2 "NULL", else phase-set rank) and
+ *             the source: SNF_GTSRC_MATCH the matched candidate's genotype (it has a match and the match has gt_set),
+ *             else SNF_GTSRC_DEPTH (0, 0, 0, depth, 0, None, None) with depth = round(mean of those of cov start / center /
+ *             end that are set) > 0, else SNF_GTSRC_NONE (config.genotype_none).  out_depth: that depth, SNF_NONE_I32 when
+ *             no sample is set - *status = 2 then (the reference returns None for the whole task), unless it is 1 already.
+ * *coverage_mean = coverage.mean() of the task.  svtype: SNF_* codes, any other value for a type outside sv.TYPES (it never
+ * matches and takes end = pos + |svlen| like DEL).  form / max_grid: as snf_genotype_match_batch. */
+enum snf_gtsrc { SNF_GTSRC_NONE = 0, SNF_GTSRC_DEPTH = 1, SNF_GTSRC_MATCH = 2 };
+typedef struct snf_gttargets {
+  int64_t n;
+  const int32_t* svtype;
+  const int32_t* pos;
+  const int32_t* svlen;
+  const int32_t* mate_contig;
+  const uint8_t* bnd_is_first;
+  int32_t* cov;                /* 5n, in / out */
+  int32_t* out_best;           /* n: index into the task's candidate list, -1 */
+  int32_t* out_dist;           /* n */
+  int32_t* out_gt;             /* 8n */
+  int32_t* out_depth;          /* n */
+} snf_gttargets_t;
+int snf_batch_genotype_targets(snf_batch_t* b, int32_t task_index, const snf_gttargets_t* io, int32_t max_grid, int32_t form,
+                               int32_t* status, double* coverage_mean);
+/* kernel time (HIP events around the match chain) of the last snf_batch_genotype_targets of this batch, in ms */
+int snf_batch_genotype_last_ms(snf_batch_t* b, double* kernel_ms);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * Seam B4: consensus.novel_from_reads(best_lead, other_leads, klen, skip, skip_repetitive)
  * (reference src/sniffles/consensus.py:280-394, called from postprocessing.py:63) for a batch of independent
  * problems.  Only the `.seq` of the leads is read, so a problem is the best sequence plus the other sequences, all

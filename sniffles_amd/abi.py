@@ -153,6 +153,33 @@ class snf_popmatch_t(C.Structure):
     ]
 
 
+class snf_gtmatch_t(C.Structure):
+    _fields_ = [
+        ("n_candidates", i64), ("c_svtype", C.POINTER(C.c_int32)), ("c_pos", C.POINTER(C.c_int32)), ("c_svlen", C.POINTER(C.c_int32)),
+        ("c_mate_contig", C.POINTER(C.c_int32)),
+        ("n_targets", i64), ("t_svtype", C.POINTER(C.c_int32)), ("t_pos", C.POINTER(C.c_int32)), ("t_svlen", C.POINTER(C.c_int32)),
+        ("t_mate_contig", C.POINTER(C.c_int32)),
+        ("out_best", C.POINTER(C.c_int32)), ("out_dist", C.POINTER(C.c_int32)),
+    ]
+
+
+class snf_gttargets_t(C.Structure):
+    _fields_ = [
+        ("n", i64), ("svtype", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)), ("svlen", C.POINTER(C.c_int32)),
+        ("mate_contig", C.POINTER(C.c_int32)), ("bnd_is_first", u8p), ("cov", C.POINTER(C.c_int32)),
+        ("out_best", C.POINTER(C.c_int32)), ("out_dist", C.POINTER(C.c_int32)), ("out_gt", C.POINTER(C.c_int32)),
+        ("out_depth", C.POINTER(C.c_int32)),
+    ]
+
+
+# the C layout of the two (include/sniffles_amd.h: one int64 count, then 8-byte members only - no padding anywhere)
+assert C.sizeof(snf_gtmatch_t) == 12 * 8 and [getattr(snf_gtmatch_t, n).offset for n, _ in snf_gtmatch_t._fields_] == list(range(0, 96, 8))
+assert C.sizeof(snf_gttargets_t) == 11 * 8 and [getattr(snf_gttargets_t, n).offset for n, _ in snf_gttargets_t._fields_] == list(range(0, 88, 8))
+NONE_I32 = -2 ** 31                                                  # SNF_NONE_I32: an unset coverage field / depth
+GTSRC_NONE, GTSRC_DEPTH, GTSRC_MATCH = 0, 1, 2                       # enum snf_gtsrc
+GT_STATUS_OK, GT_STATUS_UNBOUND_END, GT_STATUS_NO_SAMPLE, GT_STATUS_TASK_RAISED = 0, 1, 2, 3   # *status of snf_batch_genotype_targets
+
+
 def combine_problem(svtype_code: int, cands: dict, groups: dict, n_sample_ids: int, keep: list, windows=None):
     """Pack one resolve_block_groups call.  `cands`: pos, svlen, support, sample_id, mate_contig, mate_ref_start
     (int lists) and alts (list of bytes); `groups`: pos_mean, len_mean, mate_mean, size, mate_contig, alts, samples

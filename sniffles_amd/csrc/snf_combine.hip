@@ -10,7 +10,10 @@
 #include "snf_myers.h"
 #include "snf_ctx.h"
 #include "snf_group_call.h"
+#include "snf_genotype.h"
 #include "../../include/sniffles_amd.h"
+
+#include <rocprim/device/device_radix_sort.hpp>
 
 #include <cmath>
 #include <cstdlib>
@@ -314,13 +317,51 @@ __global__ void __launch_bounds__(64) popmatch_wave(const PopView v, int64_t nq)
   for (int64_t q = blockIdx.x; q < nq; q += gridDim.x) popmatch_run<true>(q, v);
 }
 
+// force calling (snf_genotype.h): one wave per target, GT_WAVES targets per workgroup / one thread per target; both stride
+__global__ void __launch_bounds__(64 * GT_WAVES) gt_match_wave(const GtMatchView v, int64_t nt) {
+  const int64_t stride = (int64_t)gridDim.x * GT_WAVES;
+  for (int64_t t = (int64_t)blockIdx.x * GT_WAVES + (threadIdx.x >> 6); t < nt; t += stride) gt_match_run<true>(t, v);
+}
+__global__ void __launch_bounds__(256) gt_match_thread(const GtMatchView v, int64_t nt) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nt; t += stride) gt_match_run<false>(t, v);
+}
+
 }  // namespace snf
 using namespace snf;
 SNF_KERNEL(combine_problem, CombineView)
 SNF_KERNEL(group_call, GroupCallView)
 SNF_KERNEL(popmatch, PopView)
+SNF_KERNEL(gt_keys, GtMatchView)
+
+namespace snf {
+size_t gt_match_tmp_bytes(int64_t nc) {
+  size_t need = 0;
+  if (nc > 0 && rocprim::radix_sort_pairs(nullptr, need, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                          (size_t)nc, 0u, GT_KEY_BITS, (hipStream_t) nullptr) != hipSuccess) return 0;
+  return need < 16 ? 16 : need;
+}
+
+int64_t gt_match_enqueue(const GtMatchView& v, void* tmp, size_t tmp_bytes, hipStream_t st, int32_t max_grid, int form) {
+  if (v.nt <= 0) return 0;
+  if (v.nc > 0) {
+    hipLaunchKernelGGL(gt_keys, dim3((unsigned)((v.nc + 255) / 256)), dim3(256), 0, st, v, v.nc);
+    if (hipGetLastError() != hipSuccess) return -1;
+    size_t need = tmp_bytes;
+    if (rocprim::radix_sort_pairs(tmp, need, (const uint32_t*)v.key_in, v.key_out, (const uint32_t*)v.idx_in, v.idx_out, (size_t)v.nc, 0u, GT_KEY_BITS, st) != hipSuccess) return -1;
+  }
+  const int64_t per = form ? 256 : GT_WAVES;      // targets per workgroup
+  int64_t grid = (v.nt + per - 1) / per;
+  if (grid > 65536) grid = 65536;
+  if (max_grid > 0 && grid > max_grid) grid = max_grid;
+  if (form) hipLaunchKernelGGL(gt_match_thread, dim3((unsigned)grid), dim3(256), 0, st, v, v.nt);
+  else hipLaunchKernelGGL(gt_match_wave, dim3((unsigned)grid), dim3(64 * GT_WAVES), 0, st, v, v.nt);
+  return hipGetLastError() == hipSuccess ? grid : -1;
+}
+}  // namespace snf
 
 namespace {
+DevArena g_gtmatch_arenas[SNF_MAX_DEVICES];
 DevArena g_combine_arenas[SNF_MAX_DEVICES];
 DevArena g_groupcall_arenas[SNF_MAX_DEVICES];
 DevArena g_popmatch_arenas[SNF_MAX_DEVICES];
@@ -595,6 +636,65 @@ extern "C" int snf_population_match_batch(const snf_config_t* cfg, int device, c
 extern "C" int snf_population_last_stats(int device, double* kernel_ms, int64_t* stats4) {
   if (device < 0 || device >= SNF_MAX_DEVICES || !kernel_ms || !stats4) return 1;
   DevArena& A = g_popmatch_arenas[device];
+  std::lock_guard<std::mutex> hold(A.mu);
+  *kernel_ms = A.last_kernel_ms;
+  for (int k = 0; k < 4; k++) stats4[k] = A.last_stats[k];
+  return 0;
+}
+
+// GenotypeTask.execute's match for host tables (include/sniffles_amd.h; device code: snf_genotype.h)
+extern "C" int snf_genotype_match_batch(const snf_config_t* cfg, int device, const snf_gtmatch_t* in, int32_t max_grid, int32_t form) {
+  if (!cfg || !in) return 1;
+  if (device < 0 || device >= SNF_MAX_DEVICES || form < 0 || form > 1) return 1;
+  const int64_t nc = in->n_candidates, nt = in->n_targets;
+  if (nt <= 0) return nt < 0;
+  if (nc < 0 || nc >= ((int64_t)1 << 31) || !in->t_svtype || !in->t_pos || !in->t_svlen || !in->t_mate_contig || !in->out_best || !in->out_dist) return 1;
+  if (nc > 0 && (!in->c_svtype || !in->c_pos || !in->c_svlen || !in->c_mate_contig)) return 1;
+  const size_t tmp_bytes = gt_match_tmp_bytes(nc);
+  if (nc > 0 && tmp_bytes == 0) return 1;
+  ArenaLayout L;
+  const size_t C = (size_t)nc, T = (size_t)nt;
+  const size_t o_ct = L.add<int32_t>(C), o_cp = L.add<int32_t>(C), o_cl = L.add<int32_t>(C), o_cm = L.add<int32_t>(C);
+  const size_t o_tt = L.add<int32_t>(T), o_tp = L.add<int32_t>(T), o_tl = L.add<int32_t>(T), o_tm = L.add<int32_t>(T);
+  const size_t in_end = (L.at + 255) & ~(size_t)255;
+  const size_t o_ki = L.add<uint32_t>(C), o_ko = L.add<uint32_t>(C), o_ii = L.add<uint32_t>(C), o_io = L.add<uint32_t>(C);
+  const size_t o_tmp = L.add<uint8_t>(tmp_bytes);
+  const size_t o_best = L.add<int32_t>(T), o_dist = L.add<int32_t>(T);
+  const size_t out_end = L.at;
+  DevArena& A = g_gtmatch_arenas[device];
+  std::lock_guard<std::mutex> hold(A.mu);
+  if (!A.ensure(device, L.at)) return 1;
+  uint8_t *h = A.h, *d = A.d;
+  if (nc) { memcpy(h + o_ct, in->c_svtype, C * 4); memcpy(h + o_cp, in->c_pos, C * 4); memcpy(h + o_cl, in->c_svlen, C * 4); memcpy(h + o_cm, in->c_mate_contig, C * 4); }
+  memcpy(h + o_tt, in->t_svtype, T * 4); memcpy(h + o_tp, in->t_pos, T * 4); memcpy(h + o_tl, in->t_svlen, T * 4); memcpy(h + o_tm, in->t_mate_contig, T * 4);
+  GtMatchView v{};
+  v.c_svtype = (const int32_t*)(d + o_ct); v.c_pos = (const int32_t*)(d + o_cp); v.c_svlen = (const int32_t*)(d + o_cl); v.c_mate = (const int32_t*)(d + o_cm);
+  v.c_stride = 1; v.nc = nc;
+  v.t_svtype = (const int32_t*)(d + o_tt); v.t_pos = (const int32_t*)(d + o_tp); v.t_svlen = (const int32_t*)(d + o_tl); v.t_mate = (const int32_t*)(d + o_tm);
+  v.nt = nt;
+  v.key_in = (uint32_t*)(d + o_ki); v.key_out = (uint32_t*)(d + o_ko); v.idx_in = (uint32_t*)(d + o_ii); v.idx_out = (uint32_t*)(d + o_io);
+  v.out_best = (int32_t*)(d + o_best); v.out_dist = (int32_t*)(d + o_dist);
+  v.merge_bnd = cfg->cluster_merge_bnd; v.combine_match = cfg->combine_match; v.combine_match_max = cfg->combine_match_max;
+  hipStream_t st = A.stream;
+  bool ok = hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st) == hipSuccess;
+  ok = ok && hipEventRecord(A.ev0, st) == hipSuccess;
+  int64_t grid = -1;
+  if (ok) { grid = gt_match_enqueue(v, d + o_tmp, tmp_bytes, st, max_grid, form); ok = grid >= 0; }
+  ok = ok && hipEventRecord(A.ev1, st) == hipSuccess;
+  ok = ok && hipMemcpyAsync(h + o_best, d + o_best, out_end - o_best, hipMemcpyDeviceToHost, st) == hipSuccess;
+  ok = ok && hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) return 1;
+  { float ms = 0; if (hipEventElapsedTime(&ms, A.ev0, A.ev1) == hipSuccess) A.last_kernel_ms = ms; }
+  A.last_stats[0] = (long long)nt; A.last_stats[1] = (long long)nc; A.last_stats[2] = (long long)grid; A.last_stats[3] = (long long)in_end;
+  memcpy(in->out_best, h + o_best, T * 4);
+  memcpy(in->out_dist, h + o_dist, T * 4);
+  return 0;
+}
+
+// measurement hook of snf_genotype_match_batch: kernel time of the chain (keys, sort, match) and its sizes
+extern "C" int snf_genotype_match_last_stats(int device, double* kernel_ms, int64_t* stats4) {
+  if (device < 0 || device >= SNF_MAX_DEVICES || !kernel_ms || !stats4) return 1;
+  DevArena& A = g_gtmatch_arenas[device];
   std::lock_guard<std::mutex> hold(A.mu);
   *kernel_ms = A.last_kernel_ms;
   for (int k = 0; k < 4; k++) stats4[k] = A.last_stats[k];

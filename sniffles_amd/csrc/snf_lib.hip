@@ -12,6 +12,7 @@
 #include "snf_wave_call_g.h"
 #include "snf_wave_refine_g.h"
 #include "snf_ctx.h"
+#include "snf_genotype.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -81,6 +82,7 @@ SNF_KERNEL(f4_emit, View)
 SNF_KERNEL(s1_blockcov, BlockCov)
 SNF_KERNEL(s2_covends, CovCalls)
 SNF_KERNEL(s2_covcalls, CovCalls)
+SNF_KERNEL(gt_tuple, GtTupleView)
 SNF_KERNEL(d5x_covexact, CovExact)
 SNF_KERNEL(r3_maxdepth, MaxDepth)
 
@@ -306,6 +308,7 @@ struct snf_batch_impl {
   int64_t h_n_occ = 0; int win_cap = 0;   // window front end: occupied windows (a property of the input, counted at upload), instance of w4 / w6
   bool reads_ready = false;       // the read index (sorted ends, hap prefix counts) of the uploaded tasks exists
   bool cov_avg_ready = false;     // a call_candidates pass has formed coverage.mean() per task
+  double gt_last_ms = 0;          // match chain of the last snf_batch_genotype_targets (HIP events)
   // host side of the inputs: the caller's arrays are BORROWED from snf_batch_add_task until snf_batch_upload returns
   // (validated, staged into pinned memory and copied by the upload); only the scalars are kept afterwards
   std::vector<snf_task_input_t> tasks;
@@ -2450,6 +2453,85 @@ void do_coverage_calls(snf_batch_t* bb, int32_t task_index, int64_t n, const int
     for (void* p : tmp) dfree_one(b, p);
 }
 
+// GenotypeTask.execute behind the candidates (include/sniffles_amd.h; device code: snf_genotype.h, s2_covends / s2_covcalls): the
+// task's finalized candidates are read where the output stage left them in HBM
+void do_genotype_targets(snf_batch_t* bb, int32_t task_index, const snf_gttargets_t* io, int32_t max_grid, int32_t form, int32_t* status,
+                         double* coverage_mean) {
+    auto b = reinterpret_cast<snf_batch_impl*>(bb);
+    if (!b || !b->uploaded || !io || !status || !coverage_mean) fail("batch not uploaded / null argument");
+    if (!b->finalized || !b->cov_avg_ready) fail("snf_batch_genotype_targets needs a finished pass (snf_batch_pass, or call_candidates + finalize)");
+    if (b->v.out_mode != (SNF_OUT_CANDIDATES | SNF_OUT_DEVICE)) fail("snf_batch_genotype_targets needs snf_batch_set_output(SNF_OUT_CANDIDATES | SNF_OUT_DEVICE) before the pass");
+    if (task_index < 0 || task_index >= b->v.T) fail("task index out of range");
+    if (form < 0 || form > 1) fail("unknown form");
+    const int64_t n = io->n;
+    if (n < 0 || (n > 0 && (!io->svtype || !io->pos || !io->svlen || !io->mate_contig || !io->bnd_is_first || !io->cov || !io->out_best ||
+                            !io->out_dist || !io->out_gt || !io->out_depth))) fail("invalid target arrays");
+    SNF_HIP(hipSetDevice(b->device));
+    full_sync(b);
+    pass_waited(b);
+    if (b->h_cnt->overflow) fail("internal: a pool of the pass overflowed");
+    for (int k = 0; k < 3; k++) if (b->skipped_big[k] && b->h_cnt->n_big[k] > 0) fail("internal: a pass skipped x_big although items were handed to it");
+    b->pass_idle = true;
+    b->gt_last_ms = 0;
+    *status = 0;
+    *coverage_mean = b->v.res_cov[task_index];
+    if (b->v.res_status[task_index] != SNF_TASK_OK) { *status = 3; return; }      // the task raised in its candidate stage: it has no candidates
+    if (n == 0) return;
+    // the task's records inside the output block (candidate order; tasks that raised hold none)
+    const int64_t c_lo = b->v.NS > 0 ? b->v.res_off[task_index] : 0, c_hi = b->v.NS > 0 ? b->v.res_off[task_index + 1] : 0;
+    const int64_t nc = c_hi - c_lo;
+    if (nc < 0 || c_hi > b->v.res_out->n_out) fail("internal: task offsets outside the output block");
+    const snf_call_t* cand = (const snf_call_t*)b->v.out_dev + c_lo;
+    CovCalls q{};
+    q.r_start = b->v.r_start; q.re_sorted = b->v.re_sorted; q.rs_top = b->v.rs_top; q.re_top = b->v.re_top;
+    q.lo = b->h_read_off[(size_t)task_index]; q.hi = b->h_read_off[(size_t)task_index + 1];
+    q.L = b->tasks[(size_t)task_index].contig_len; q.n = n;
+    q.nm_start = b->v.nm_start; q.nm_end = b->v.nm_end; q.nm_lo = b->h_nm_off[(size_t)task_index]; q.nm_hi = b->h_nm_off[(size_t)task_index + 1];
+    q.binsize = b->cfg.coverage_binsize; q.updown = b->cfg.coverage_updown_bins;
+    const size_t N = (size_t)n, C = (size_t)nc;
+    int32_t* d_t = dalloc_own<int32_t>(b, N); int32_t* d_p = dalloc_own<int32_t>(b, N); int32_t* d_l = dalloc_own<int32_t>(b, N);
+    int32_t* d_m = dalloc_own<int32_t>(b, N); uint8_t* d_f = dalloc_own<uint8_t>(b, N);
+    q.end = dalloc_own<int64_t>(b, N); q.cov = dalloc_own<int32_t>(b, N * 5); q.n_valid = dalloc_own<int32_t>(b, 4);
+    const size_t tmp_bytes = gt_match_tmp_bytes(nc);
+    if (nc > 0 && tmp_bytes == 0) fail("internal: radix sort scratch size");
+    GtMatchView m{};
+    const int64_t stride = (int64_t)(sizeof(snf_call_t) / sizeof(int32_t));
+    m.c_svtype = &cand->svtype; m.c_pos = &cand->pos; m.c_svlen = &cand->svlen; m.c_mate = &cand->mate_contig; m.c_stride = stride; m.nc = nc;
+    m.t_svtype = d_t; m.t_pos = d_p; m.t_svlen = d_l; m.t_mate = d_m; m.nt = n;
+    m.key_in = dalloc_own<uint32_t>(b, C); m.key_out = dalloc_own<uint32_t>(b, C); m.idx_in = dalloc_own<uint32_t>(b, C); m.idx_out = dalloc_own<uint32_t>(b, C);
+    m.out_best = dalloc_own<int32_t>(b, N); m.out_dist = dalloc_own<int32_t>(b, N);
+    m.merge_bnd = b->cfg.cluster_merge_bnd; m.combine_match = b->cfg.combine_match; m.combine_match_max = b->cfg.combine_match_max;
+    uint8_t* d_tmp = dalloc_own<uint8_t>(b, tmp_bytes);
+    GtTupleView g{};
+    g.cand = cand; g.nc = nc; g.best = m.out_best; g.cov = q.cov; g.n_valid = q.n_valid; g.no_sample = q.n_valid + 2; g.n = n;
+    g.gt = dalloc_own<int32_t>(b, N * 8); g.depth = dalloc_own<int32_t>(b, N);
+    h2d(b, d_t, io->svtype, N * 4); h2d(b, d_p, io->pos, N * 4); h2d(b, d_l, io->svlen, N * 4); h2d(b, d_m, io->mate_contig, N * 4);
+    h2d(b, d_f, io->bnd_is_first, N); h2d(b, q.cov, io->cov, N * 20);
+    dzero(b, q.n_valid, 16);
+    q.svtype = d_t; q.pos = d_p; q.svlen = d_l; q.bnd_is_first = d_f;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    SNF_HIP(hipEventCreate(&e0)); SNF_HIP(hipEventCreate(&e1));
+    SNF_HIP(hipEventRecord(e0, b->cur));
+    const int64_t grid = gt_match_enqueue(m, d_tmp, tmp_bytes, b->cur, max_grid, form);
+    SNF_HIP(hipEventRecord(e1, b->cur));
+    if (grid >= 0) {
+      KERNEL_N(s2_covends, q, 1, n * 13, heavy);
+      KERNEL_N(s2_covcalls, q, n, (q.hi - q.lo) * 8 + n * 40, heavy);
+      KERNEL_N(gt_tuple, g, n, n * 64, heavy);
+    }
+    int32_t nv[4] = {0, 0, 0, 0};
+    d2h(b, io->cov, q.cov, N * 20); d2h(b, io->out_best, m.out_best, N * 4); d2h(b, io->out_dist, m.out_dist, N * 4);
+    d2h(b, io->out_gt, g.gt, N * 32); d2h(b, io->out_depth, g.depth, N * 4);
+    d2h(b, nv, q.n_valid, 16);
+    dsync(b);
+    { float ms = 0; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) b->gt_last_ms = ms; }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    void* tmp[] = {d_t, d_p, d_l, d_m, d_f, q.end, q.cov, q.n_valid, m.key_in, m.key_out, m.idx_in, m.idx_out, m.out_best, m.out_dist, d_tmp, g.gt, g.depth};
+    for (void* p : tmp) dfree_one(b, p);
+    if (grid < 0) fail("snf_batch_genotype_targets: the match could not be launched");
+    *status = nv[1] ? 1 : (nv[2] ? 2 : 0);
+}
+
 // ---- stand-alone genotyping (--reqc): genotype_sv of snf_stage_final.h over caller-supplied records
 struct GenoView { snf_config_t cfg; const GtEntry* gt_lut; snf_call_t* calls; int64_t n; };
 namespace snf {
@@ -2931,6 +3013,18 @@ int snf_batch_block_coverage(snf_batch_t* bb, int32_t task_index, int32_t binsiz
 int snf_batch_coverage_calls(snf_batch_t* bb, int32_t task_index, int64_t n, const int32_t* svtype, const int32_t* pos,
                              const int32_t* svlen, const uint8_t* bnd_is_first, int32_t* cov, int32_t* status, double* coverage_mean) {
   SNF_TRY(do_coverage_calls(bb, task_index, n, svtype, pos, svlen, bnd_is_first, cov, status, coverage_mean))
+}
+
+int snf_batch_genotype_targets(snf_batch_t* bb, int32_t task_index, const snf_gttargets_t* io, int32_t max_grid, int32_t form, int32_t* status,
+                               double* coverage_mean) {
+  SNF_TRY(do_genotype_targets(bb, task_index, io, max_grid, form, status, coverage_mean))
+}
+
+int snf_batch_genotype_last_ms(snf_batch_t* bb, double* kernel_ms) {
+  auto b = reinterpret_cast<snf_batch_impl*>(bb);
+  if (!b || !kernel_ms) { g_err = "null argument"; return 1; }
+  *kernel_ms = b->gt_last_ms;
+  return 0;
 }
 
 int snf_consensus_batch(int device, int klen, const uint8_t* seq_pool, int64_t seq_pool_len, int64_t n_problems,

@@ -75,6 +75,15 @@ def bind(lib: C.CDLL) -> C.CDLL:
     lib.snf_population_match_batch.restype = C.c_int
     lib.snf_population_last_stats.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.snf_population_last_stats.restype = C.c_int
+    lib.snf_genotype_match_batch.argtypes = [C.POINTER(abi.snf_config_t), C.c_int, C.POINTER(abi.snf_gtmatch_t), C.c_int32, C.c_int32]
+    lib.snf_genotype_match_batch.restype = C.c_int
+    lib.snf_genotype_match_last_stats.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.snf_genotype_match_last_stats.restype = C.c_int
+    lib.snf_batch_genotype_targets.argtypes = [vp, C.c_int32, C.POINTER(abi.snf_gttargets_t), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_double)]
+    lib.snf_batch_genotype_targets.restype = C.c_int
+    lib.snf_batch_genotype_last_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.snf_batch_genotype_last_ms.restype = C.c_int
     u8p, i64p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
     lib.snf_consensus_batch.argtypes = [C.c_int, C.c_int, u8p, C.c_int64, C.c_int64, i64p, i32p, i32p, i32p, i64p, i64p, i32p, u8p, i64p]
     lib.snf_consensus_batch.restype = C.c_int
@@ -367,6 +376,30 @@ class Batch:
                                                            cv.ctypes.data_as(i32p), C.byref(st), C.byref(mean)))
         return cv[:5 * n].reshape(n, 5), int(st.value), float(mean.value)
 
+    def genotype_targets(self, task_index: int, svtype, pos, svlen, mate_contig, bnd_is_first, cov, max_grid: int = 0, form: int = 0) -> dict:
+        """`GenotypeTask.execute` behind the candidates for a column table of targets, against the task's finalized candidates where they
+        lie in HBM (snf_batch_genotype_targets; needs `set_output(OUT_CANDIDATES | OUT_DEVICE)` before the pass).  Returns best, dist,
+        cov [n, 5], gt [n, 8] (a, b, GQ, DR, DV, hp, ps, source), depth, status (abi.GT_STATUS_*), coverage_mean, kernel_ms."""
+        i32p, n = C.POINTER(C.c_int32), len(pos)
+        a = [np.ascontiguousarray(np.asarray(x, np.int32).reshape(-1)) for x in (svtype, pos, svlen, mate_contig)]
+        f = np.ascontiguousarray(np.asarray(bnd_is_first, np.uint8).reshape(-1))
+        cv = np.ascontiguousarray(np.asarray(cov, np.int32).reshape(-1)).copy()
+        if n == 0:
+            a, f, cv = [np.zeros(1, np.int32)] * 4, np.zeros(1, np.uint8), np.zeros(5, np.int32)
+        if any(len(x) < n for x in a) or len(f) < n or len(cv) < 5 * n:
+            raise ValueError("genotype_targets: the target columns do not fit together")
+        best, dist = np.full(max(n, 1), -1, np.int32), np.zeros(max(n, 1), np.int32)
+        gt, depth = np.zeros(8 * max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        io = abi.snf_gttargets_t(n=n, svtype=a[0].ctypes.data_as(i32p), pos=a[1].ctypes.data_as(i32p), svlen=a[2].ctypes.data_as(i32p),
+                                 mate_contig=a[3].ctypes.data_as(i32p), bnd_is_first=f.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                 cov=cv.ctypes.data_as(i32p), out_best=best.ctypes.data_as(i32p), out_dist=dist.ctypes.data_as(i32p),
+                                 out_gt=gt.ctypes.data_as(i32p), out_depth=depth.ctypes.data_as(i32p))
+        st, mean, ms = C.c_int32(), C.c_double(), C.c_double()
+        _check(self.lib, self.lib.snf_batch_genotype_targets(self._h, task_index, C.byref(io), int(max_grid), int(form), C.byref(st), C.byref(mean)))
+        self.lib.snf_batch_genotype_last_ms(self._h, C.byref(ms))
+        return dict(best=best[:n], dist=dist[:n], cov=cv[:5 * n].reshape(n, 5), gt=gt[:8 * n].reshape(n, 8), depth=depth[:n],
+                    status=int(st.value), coverage_mean=float(mean.value), kernel_ms=float(ms.value))
+
     def timings(self) -> list:
         out = []
         for i in range(self.lib.snf_batch_timing_count(self._h)):
@@ -554,6 +587,44 @@ def population_last_stats(device: int = 0) -> dict:
     if lib.snf_population_last_stats(device, C.byref(ms), st) != 0:
         raise SnifflesAmdError("snf_population_last_stats failed")
     return dict(kernel_ms=float(ms.value), alignments=int(st[0]), aligned_bytes=int(st[1]), dp_cells=int(st[2]), staged_bytes=int(st[3]))
+
+
+def genotype_match_batch(cfg, candidates: dict, targets: dict, device: int = 0, max_grid: int = 0, form: int = 0):
+    """The match of `GenotypeTask.execute` for host tables (snf_genotype_match_batch): `candidates` / `targets` hold svtype (SNF_* codes;
+    anything else for a type outside sv.TYPES), pos, svlen, mate_contig - int32 per row, candidates in candidate order.  `form` 0: one wave
+    per target, 1: one thread per target; `max_grid` > 0 caps the workgroups of the match.  Returns (best: int32 per target - index into
+    the candidates, -1 none -, dist: int32 per target)."""
+    lib = load()
+
+    def cols(t):
+        c = [np.ascontiguousarray(np.asarray(t[k], np.int32).reshape(-1)) for k in ("svtype", "pos", "svlen", "mate_contig")]
+        if len({len(x) for x in c}) != 1:
+            raise ValueError("genotype_match_batch: columns of different lengths")
+        n = len(c[0])
+        return n, [x if n else np.zeros(1, np.int32) for x in c]
+    nc, c = cols(candidates)
+    nt, t = cols(targets)
+    best, dist = np.full(max(nt, 1), -1, np.int32), np.zeros(max(nt, 1), np.int32)
+    if nt == 0:
+        return best[:0], dist[:0]
+    p32 = C.POINTER(C.c_int32)
+    arg = abi.snf_gtmatch_t(n_candidates=nc, c_svtype=c[0].ctypes.data_as(p32), c_pos=c[1].ctypes.data_as(p32), c_svlen=c[2].ctypes.data_as(p32),
+                            c_mate_contig=c[3].ctypes.data_as(p32), n_targets=nt, t_svtype=t[0].ctypes.data_as(p32),
+                            t_pos=t[1].ctypes.data_as(p32), t_svlen=t[2].ctypes.data_as(p32), t_mate_contig=t[3].ctypes.data_as(p32),
+                            out_best=best.ctypes.data_as(p32), out_dist=dist.ctypes.data_as(p32))
+    cs = abi.config_struct(cfg)
+    if lib.snf_genotype_match_batch(C.byref(cs), device, C.byref(arg), int(max_grid), int(form)) != 0:
+        raise SnifflesAmdError("snf_genotype_match_batch failed (no HIP device, or invalid arguments)")
+    return best[:nt], dist[:nt]
+
+
+def genotype_match_last_stats(device: int = 0) -> dict:
+    """Kernel time (keys + sort + match, HIP events) and sizes of the last genotype_match_batch on `device`."""
+    lib = load()
+    ms, st = C.c_double(), (C.c_int64 * 4)()
+    if lib.snf_genotype_match_last_stats(device, C.byref(ms), st) != 0:
+        raise SnifflesAmdError("snf_genotype_match_last_stats failed")
+    return dict(kernel_ms=float(ms.value), targets=int(st[0]), candidates=int(st[1]), workgroups=int(st[2]), staged_bytes=int(st[3]))
 
 
 def genotype_batch(cfg, records: np.ndarray, device: int = 0) -> np.ndarray:

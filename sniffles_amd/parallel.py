@@ -365,6 +365,65 @@ class GenotypeTask(Task):
             target.genotypes = {0: (0, 0, 0, depth, 0, (None, None)) if depth > 0 else config.genotype_none}
         return self.genotype_svs
 
+    def execute_records(self, table: dict, max_grid: int = 0, form: int = 0):
+        """`execute` for a column table of targets, without `SVCall` objects on either side: the task's candidates stay in HBM behind
+        the pass, the match, the coverage samples and the genotype tuple of every target are formed there
+        (`snf_batch_genotype_targets`) and only the result columns come back.
+        `table` (what `vcf.VCF.read_target_table` makes per contig): `svtype` (SNF_* code, -1 for a type outside `sv.TYPES`), `pos`,
+        `svlen`, `mate_contig` (index into `table["mate_names"]`, -1 without a mate), `bnd_is_first` and `cov` ([n, 5] upstream, start,
+        center, end, downstream; `abi.NONE_I32` = unset).
+        Returns None where `execute` does (a target without any coverage sample), raises UnboundLocalError where it does (a BND
+        target before any other, a task whose first candidate is a BND), else a dict of columns per target: `best` (index into the
+        task's candidate list, -1), `dist`, `cov` [n, 5], `gt` [n, 8] (a, b, GQ, DR, DV, hp, ps, source - `abi.GTSRC_*`), `depth`,
+        plus `kernel_ms` (the match chain) and `n_candidates`.  `genotype_tuples(result)` turns `gt` into what
+        `vcf.format_genotype` takes.  `max_grid` / `form`: test hooks of the match kernel."""
+        import numpy as np
+
+        from . import abi
+        config = self.config
+        self._open(config)
+        self._batch.set_output(abi.OUT_CANDIDATES | abi.OUT_DEVICE)
+        self._batch.run_pass()
+        names = list(table.get("mate_names") or [])
+        lut = np.asarray([self._contig_rank(n, k) for k, n in enumerate(names)] + [-1], np.int32)      # (-1 -> -1: no mate)
+        mate = lut[np.asarray(table["mate_contig"], np.int64)] if len(table["pos"]) else np.zeros(0, np.int32)
+        r = self._batch.genotype_targets(0, table["svtype"], table["pos"], table["svlen"], mate, table["bnd_is_first"], table["cov"],
+                                         max_grid=max_grid, form=form)
+        if r["status"] in (abi.GT_STATUS_UNBOUND_END, abi.GT_STATUS_TASK_RAISED):
+            raise UnboundLocalError("local variable 'end' referenced before assignment")
+        self._finalized = True
+        r["n_candidates"] = int(self._batch.n_candidates())
+        self.sv_id += r["n_candidates"]
+        self.coverage_average_total = r["coverage_mean"]
+        if r["status"] == abi.GT_STATUS_NO_SAMPLE:
+            return None
+        return r
+
+    def _contig_rank(self, name: str, k: int) -> int:
+        """The task's number of mate contig `name`; a name the task does not know gets a value no candidate has."""
+        ti = self._ti
+        if ti.contig_names is not None:
+            try:
+                return list(ti.contig_names).index(name)
+            except ValueError:
+                return -2 - k
+        return int(name[3:]) if name.startswith("ctg") and name[3:].isdigit() else -2 - k
+
+    def genotype_tuples(self, result: dict) -> list:
+        """The `gt` column of `execute_records` as the tuples `vcf.format_genotype` takes: (a, b, GQ, DR, DV, (hp, ps)) of the matched
+        candidate, (0, 0, 0, depth, 0, (None, None)), or `config.genotype_none`."""
+        from . import abi
+        none = self.config.genotype_none
+        out = []
+        for a, b, gq, dr, dv, hp, ps, src in result["gt"].tolist():
+            if src == abi.GTSRC_NONE:
+                out.append(none)
+            elif src == abi.GTSRC_DEPTH:
+                out.append((0, 0, 0, dr, 0, (None, None)))
+            else:
+                out.append((a, b, gq, dr, dv, (None if hp < 0 else str(hp), sv._ps(ps, self._ti))))
+        return out
+
 
 class CombineTask(Task):
     """`CombineTask.execute` of the reference (parallel.py:444-572): the block / bin / flush-window driver of the

@@ -317,15 +317,28 @@ def combine(snf_paths, config, vcf_handle=None, sample_ids=None, device: int = 0
     return out if objects else []
 
 
-def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle, tandem_repeats=None, device: int = 0, reference=None) -> int:
+def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle, tandem_repeats=None, device: int = 0, reference=None,
+                 objects: bool = True, timing: dict = None) -> int:
     """Force calling (`--genotype-vcf`, sniffles:190-213, 487-560 and `GenotypeTask.execute`): the SVs of the input VCF are
     matched against this sample's candidates contig by contig and written back with the sample's genotype (contig by
-    contig, input order within a contig).  Returns the number of records written."""
+    contig, input order within a contig).  Returns the number of records written.
+    `objects=False`: the same text without an `SVCall` on either side - the targets are read as column tables
+    (`VCF.read_target_table`), the signatures stay in HBM between extraction and pass (no `--regions`), the candidates stay there
+    behind the pass, and match, coverage and genotype of every target are formed on the device (`GenotypeTask.execute_records`).
+    `timing`: a dict that receives the seconds spent per stage (read, extract, pass_match, text) and the match chain's kernel ms."""
+    import time
     config.mode = "genotype_vcf"
+    clock = time.perf_counter
+    spent = dict(read=0.0, extract=0.0, pass_match=0.0, text=0.0, match_kernel_ms=0.0)
+    t0 = clock()
     reader = vcf.VCF(config, vcf_in_handle)
     by_contig = {}
-    for target in reader.read_svs_iter():
-        by_contig.setdefault(target.contig, []).append(target)
+    if objects:
+        for target in reader.read_svs_iter():
+            by_contig.setdefault(target.contig, []).append(target)
+    else:
+        by_contig = reader.read_target_table()
+    spent["read"] += clock() - t0
     total_mapped = _total_mapped(records)
     config.task_read_id_offset_mult = 10 ** 9 if total_mapped == 0 else 10 ** math.ceil(math.log(total_mapped) + 1)
     contig_lengths = [(c, int(n)) for c, n in zip(records.ref_names, records.ref_lens) if should_process_contig(c, int(n), config)]
@@ -336,22 +349,67 @@ def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle,
     n = 0
     for task_id, (contig, length) in enumerate(contig_lengths):
         tr = (tandem_repeats or {}).get(contig)
-        targets = [t for t in by_contig.get(contig, []) if 0 <= t.pos < length - 1]
+        t0 = clock()
+        if objects:
+            targets = [t for t in by_contig.get(contig, []) if 0 <= t.pos < length - 1]
+        else:
+            table = by_contig.get(contig)
+            if table is not None:
+                table = vcf.VCF.select_targets(table, (table["pos"] >= 0) & (table["pos"] < length - 1))
+            targets = []
+        spent["read"] += clock() - t0
         task = parallel.GenotypeTask(id=task_id, sv_id=0, contig=contig, start=0, end=length - 1, config=config, tandem_repeats=tr,
                                      genotype_svs=targets, device=device)
         regions = regions_of(config, contig) or [(task.start, task.end)]       # --regions: leads and coverage from these intervals only
         source = _ContigInput(records, contig, regions_of(config, contig))
-        try:
-            ti, _, _ = _extract_regions(source.recs, contig, regions, config,
-                                        (task_id * config.task_read_id_offset_mult) % 2 ** 32, task_id, tr, device)
-        finally:
-            source.close()      # (the task input is on the host: the contig's records are not needed any more)
+        t0 = clock()
+        if not objects and not regions_of(config, contig):
+            # the signatures never leave HBM between the extraction and the clustering batch, as in `call_sample`
+            try:
+                ti, _, extractor = extract.extract_region_device(source.recs, contig, task.start, task.end, config,
+                                                                 read_id_offset=(task_id * config.task_read_id_offset_mult) % 2 ** 32,
+                                                                 task_id=task_id, sv_id_start=0, tandem_repeats=tr, device=device)
+            except Exception:
+                source.close()
+                raise
+        else:
+            extractor = None
+            try:
+                ti, _, _ = _extract_regions(source.recs, contig, regions, config,
+                                            (task_id * config.task_read_id_offset_mult) % 2 ** 32, task_id, tr, device)
+            finally:
+                source.close()      # (the task input is on the host: the contig's records are not needed any more)
         config.qc_nm_threshold = config.average_regional_nm = ti.qc_nm_threshold
         mask_N_coverage(ti, fasta_handle, contig, regions)
         task.lead_provider = _Extracted(ti)
-        res = task.execute()
-        task.close()
-        for target in res or []:      # task by task, input order inside a task (GenotypeResult.emit, result.py:118-131);
-            writer.rewrite_genotype(target)      # targets on contigs that are not processed are dropped, like the reference
-            n += 1
+        spent["extract"] += clock() - t0
+        t0 = clock()
+        try:
+            if objects:
+                res = task.execute()
+            else:
+                import numpy as np
+                if table is None:
+                    table = dict(svtype=np.zeros(0, np.int32), pos=np.zeros(0, np.int64), svlen=np.zeros(0, np.int64), mate_contig=np.zeros(0, np.int32),
+                                 bnd_is_first=np.zeros(0, np.uint8), cov=np.zeros((0, 5), np.int32), lines=[], mate_names=[])
+                res = task.execute_records(table)
+                tuples = task.genotype_tuples(res) if res is not None else []
+                if res is not None:
+                    spent["match_kernel_ms"] += res["kernel_ms"]
+        finally:
+            task.close()
+            if extractor is not None:
+                extractor.close()      # (backs the lazy host copies of the task input: goes after the task)
+                source.close()         # (an indexed file's contig leaves HBM with its task)
+        spent["pass_match"] += clock() - t0
+        t0 = clock()
+        if objects:
+            for target in res or []:      # task by task, input order inside a task (GenotypeResult.emit, result.py:118-131);
+                writer.rewrite_genotype(target)      # targets on contigs that are not processed are dropped, like the reference
+                n += 1
+        elif res is not None:
+            n += writer.rewrite_genotype_records(table["lines"], tuples)
+        spent["text"] += clock() - t0
+    if timing is not None:
+        timing.update(spent)
     return n

@@ -380,11 +380,44 @@ class VCF:
         return n
 
     # ---- force calling: targets in, the same lines with this sample's genotype out (vcf.py:352-481)
-    def read_svs_iter(self):
-        """Target SVs of `--genotype-vcf`: one `SVCall` per record of `self.handle` (text or bytes lines); header lines
-        are collected in `self.header_str`.  Type and length come from REF / ALT unless INFO gives SVTYPE (`TRA` = BND),
-        SVLEN, END; a BND's mate is parsed from its ALT.  `call.id` is the 1-based line number, like the reference."""
-        from . import sv
+    @staticmethod
+    def _parse_target(line):
+        """One non-header record of a target VCF as `read_svs_iter` reads it (vcf.py:352-430), in the reference's order of evaluation
+        (so that a malformed line fails with the same exception): (chrom, pos0, ref, alt, qual, filter, info, svtype, svlen, end, bnd)
+        with `bnd` = (mate_contig, mate_ref_start, is_first, is_reverse) or None."""
+        chrom, pos, _, ref, alt, qual, flt, info_text = line.split("\t")[:8]
+        info = {}
+        for item in info_text.split(";"):
+            if "=" in item:
+                key, value = item.split("=")
+            else:
+                key, value = item, True
+            info[key] = value
+        pos0 = int(pos) - 1
+        qual = int(qual) if qual != "." else None
+        if len(alt) > len(ref):
+            svtype, svlen, end = "INS", len(alt), pos0
+        else:
+            svtype, svlen = "DEL", -len(ref)
+            end = pos0 + svlen
+        if "SVTYPE" in info:
+            svtype = "BND" if info["SVTYPE"] == "TRA" else info["SVTYPE"]
+        if "SVLEN" in info:
+            svlen = int(info["SVLEN"])
+        if "END" in info:
+            end = int(info["END"])
+        bnd = None
+        if svtype == "BND":
+            parts = alt.replace("]", "[").split("[")
+            if len(parts) <= 2:
+                raise ValueError("BND ALT not formatted according to VCF 4.2 specifications")
+            mate_contig, mate_pos = parts[1].split(":")
+            bnd = (mate_contig, int(mate_pos), alt[0] == "N", "]" in alt)
+        return chrom, pos0, ref, alt, qual, flt, info, svtype, svlen, end, bnd
+
+    def _target_lines(self):
+        """(1-based line number, the line, its stripped text) of every record of `self.handle` (text or bytes lines); header lines go
+        to `self.header_str`.  A malformed line raises as the reference's reader does; the caller parses inside the same guard."""
         self.header_str = ""
         for line_index, line in enumerate(self.handle, 1):
             try:
@@ -396,39 +429,75 @@ class VCF:
                 if text[0] == "#":
                     self.header_str += text + "\n"
                     continue
-                chrom, pos, _, ref, alt, qual, flt, info_text = line.split("\t")[:8]
-                info = {}
-                for item in info_text.split(";"):
-                    if "=" in item:
-                        key, value = item.split("=")
-                    else:
-                        key, value = item, True
-                    info[key] = value
-                call = sv.SVCall(contig=chrom, pos=int(pos) - 1, id=line_index, ref=ref, alt=alt, qual=int(qual) if qual != "." else None,
-                                 filter=flt, info=info, svtype=None, svlen=None, end=None, rnames=None, qc=True, postprocess=None,
-                                 genotypes=None, precise=None, support=0, fwd=0, rev=0, nm=-1)
-                if len(alt) > len(ref):
-                    call.svtype, call.svlen, call.end = "INS", len(alt), call.pos
-                else:
-                    call.svtype, call.svlen = "DEL", -len(ref)
-                    call.end = call.pos + call.svlen
-                if "SVTYPE" in info:
-                    call.svtype = "BND" if info["SVTYPE"] == "TRA" else info["SVTYPE"]
-                if "SVLEN" in info:
-                    call.svlen = int(info["SVLEN"])
-                if "END" in info:
-                    call.end = int(info["END"])
-                if call.svtype == "BND":
-                    parts = alt.replace("]", "[").split("[")
-                    if len(parts) <= 2:
-                        raise ValueError("BND ALT not formatted according to VCF 4.2 specifications")
-                    mate_contig, mate_pos = parts[1].split(":")
-                    call.bnd_info = sv.SVCallBNDInfo(mate_contig=mate_contig, mate_ref_start=int(mate_pos), is_first=(alt[0] == "N"),
-                                                     is_reverse=("]" in alt))
-                call.raw_vcf_line, call.raw_vcf_line_index = text, line_index
+                parsed = self._parse_target(line)
             except Exception as e:
                 raise ValueError(f"Error parsing input VCF: Line {line_index}: {e}") from e     # the reference exits here
+            yield line_index, text, parsed
+
+    def read_svs_iter(self):
+        """Target SVs of `--genotype-vcf`: one `SVCall` per record of `self.handle` (text or bytes lines); header lines
+        are collected in `self.header_str`.  Type and length come from REF / ALT unless INFO gives SVTYPE (`TRA` = BND),
+        SVLEN, END; a BND's mate is parsed from its ALT.  `call.id` is the 1-based line number, like the reference."""
+        from . import sv
+        for line_index, text, (chrom, pos0, ref, alt, qual, flt, info, svtype, svlen, end, bnd) in self._target_lines():
+            call = sv.SVCall(contig=chrom, pos=pos0, id=line_index, ref=ref, alt=alt, qual=qual,
+                             filter=flt, info=info, svtype=svtype, svlen=svlen, end=end, rnames=None, qc=True, postprocess=None,
+                             genotypes=None, precise=None, support=0, fwd=0, rev=0, nm=-1)
+            if bnd is not None:
+                call.bnd_info = sv.SVCallBNDInfo(mate_contig=bnd[0], mate_ref_start=bnd[1], is_first=bnd[2], is_reverse=bnd[3])
+            call.raw_vcf_line, call.raw_vcf_line_index = text, line_index
             yield call
+
+    def read_target_table(self) -> dict:
+        """The records `read_svs_iter` reads, as one column table per contig (contigs in order of first appearance, records in input
+        order) and without an `SVCall`: {contig: dict(line_index, svtype, pos, svlen, end, mate_contig, mate_ref_start, bnd_is_first,
+        bnd_is_reverse, cov, lines, mate_names)}.  `svtype`: the SNF_* code of a type in `sv.TYPES`, else -1 (`svtype_names` keeps the
+        strings); `mate_contig`: index into the contig's `mate_names`, -1 without a mate; `cov`: [n, 5] zeros - the coverage fields a
+        fresh `SVCall` has (sv.py:117-121); `lines`: the stripped text of every record (`raw_vcf_line`).  Same rules, same 1-based line
+        numbers and the same ValueError for a malformed line as `read_svs_iter`."""
+        import numpy as np
+
+        from . import sv
+        code = {n: k for k, n in enumerate(sv.TYPES)}
+        rows = {}
+        for line_index, text, (chrom, pos0, _, _, _, _, _, svtype, svlen, end, bnd) in self._target_lines():
+            t = rows.get(chrom)
+            if t is None:
+                t = rows[chrom] = dict(line_index=[], svtype=[], svtype_names=[], pos=[], svlen=[], end=[], mate_contig=[], mate_ref_start=[],
+                                       bnd_is_first=[], bnd_is_reverse=[], lines=[], mate_names=[], _mates={})
+            t["line_index"].append(line_index); t["svtype"].append(code.get(svtype, -1)); t["svtype_names"].append(svtype)
+            t["pos"].append(pos0); t["svlen"].append(svlen); t["end"].append(end); t["lines"].append(text)
+            if bnd is None:
+                t["mate_contig"].append(-1); t["mate_ref_start"].append(0); t["bnd_is_first"].append(0); t["bnd_is_reverse"].append(0)
+            else:
+                k = t["_mates"].get(bnd[0])
+                if k is None:
+                    k = t["_mates"][bnd[0]] = len(t["mate_names"])
+                    t["mate_names"].append(bnd[0])
+                t["mate_contig"].append(k); t["mate_ref_start"].append(bnd[1]); t["bnd_is_first"].append(int(bnd[2])); t["bnd_is_reverse"].append(int(bnd[3]))
+        for t in rows.values():
+            del t["_mates"]
+            for k in ("line_index", "pos", "svlen", "end", "mate_ref_start"):
+                t[k] = np.asarray(t[k], np.int64)
+            t["svtype"], t["mate_contig"] = np.asarray(t["svtype"], np.int32), np.asarray(t["mate_contig"], np.int32)
+            t["bnd_is_first"], t["bnd_is_reverse"] = np.asarray(t["bnd_is_first"], np.uint8), np.asarray(t["bnd_is_reverse"], np.uint8)
+            t["cov"] = np.zeros((len(t["lines"]), 5), np.int32)
+        return rows
+
+    @staticmethod
+    def select_targets(table: dict, keep) -> dict:
+        """The rows `keep` (boolean mask or indices) of one contig's target table, order kept."""
+        import numpy as np
+        idx = np.flatnonzero(keep) if np.asarray(keep).dtype == bool else np.asarray(keep, np.int64)
+        out = {}
+        for k, v in table.items():
+            if k == "mate_names":
+                out[k] = v
+            elif isinstance(v, list):
+                out[k] = [v[i] for i in idx.tolist()]
+            else:
+                out[k] = v[idx]
+        return out
 
     def rewrite_header_genotype(self, orig_header: str):
         lines = orig_header.split("\n")
@@ -447,3 +516,21 @@ class VCF:
         gt = match.genotypes[0] if (match is not None and len(match.genotypes) > 0) else svcall.genotypes[0]
         cols = svcall.raw_vcf_line.split("\t")[:8] + [self.config.genotype_format, format_genotype(gt, self.config.phase)]
         self.write_raw("\t".join(cols))
+
+    def rewrite_genotype_records(self, lines, genotypes) -> int:
+        """`rewrite_genotype` for the targets of one contig from their raw lines and genotype tuples (`GenotypeTask.genotype_tuples`):
+        the first eight columns + FORMAT + the sample column, assembled here and written once.  Returns the number of lines."""
+        fmt, phase = self.config.genotype_format, self.config.phase
+        cache = {}
+        out = []
+        for text, gt in zip(lines, genotypes):
+            col = cache.get(gt)
+            if col is None:
+                col = cache[gt] = fmt + "\t" + format_genotype(gt, phase)
+            out.append("\t".join(text.split("\t")[:8]))
+            out.append("\t")
+            out.append(col)
+            out.append("\n")
+        if out:
+            self.handle.write("".join(out))
+        return len(out) // 4
