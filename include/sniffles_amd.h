@@ -1005,6 +1005,64 @@ int snf_fasta_read_text(snf_fasta_t* f, int64_t off, int64_t len, uint8_t* dst);
 void snf_fasta_destroy(snf_fasta_t* f);
 const char* snf_fasta_last_error(void);
 
+/* -----------------------------------------------------------------------------------------------------------------
+ * The target VCF of force calling resident on the device (csrc/snf_vcftext.h): the whole text as one buffer in HBM, its
+ * line table, the columns `VCF._parse_target` (sniffles_amd/vcf.py; reference vcf.py:352-430) reads off every record line,
+ * and the genotyped lines written back from the text where it lies.  The host parser stays the judge: a line is
+ * SNF_VT_RECORD only where the kernel is certain that `_parse_target` would not raise and would give the same values (plain
+ * bytes, at least eight columns, integers of the form -?[0-9]{1,18}, no INFO item with two '=', none of SVTYPE / SVLEN /
+ * END as a bare flag, a BND's ALT with one ':' between its first two brackets); everything else is SNF_VT_HOST and is
+ * parsed by the caller, line by line.  Additive to version 5.  No environment switch: `max_grid` (0: uncapped) caps the
+ * grids, beyond it a workgroup takes several chunks, a wave several lines or rows.  Results are library-owned until the next
+ * call on the handle.  CRC-32 of BGZF members is not checked, as in snf_bgzf_inflate.
+ * ----------------------------------------------------------------------------------------------------------------- */
+enum snf_vcftext_class { SNF_VT_HOST = 0, SNF_VT_HEADER = 1, SNF_VT_RECORD = 2 };
+enum snf_vcftext_flags { SNF_VT_BND_FIRST = 1, SNF_VT_BND_REVERSE = 2, SNF_VT_NEW_CHROM = 4 };
+
+typedef struct snf_vcftext_line {   /* one line of the text (64 bytes); every offset but `start` is relative to `start` */
+  int64_t start;                    /* text offset of the line's first byte; the line ends where the next one starts (the last: text_len) */
+  int64_t pos, svlen, end;          /* SNF_VT_RECORD: pos0, svlen, end as `_parse_target` gives them */
+  int64_t mate_pos;                 /* BND: mate_ref_start */
+  uint32_t send;                    /* SNF_VT_RECORD / SNF_VT_HEADER: end of the stripped text */
+  uint32_t cut8;                    /* SNF_VT_RECORD: the eighth tab of the stripped text, or its end: what the rewrite keeps */
+  uint32_t chrom_end;               /* SNF_VT_RECORD: the first tab */
+  uint32_t span_a, span_len;        /* BND: the mate's name; svtype -1: the type's name */
+  int8_t svtype;                    /* index into INS, DEL, DUP, INV, BND; -1: another name */
+  uint8_t cls, flags, _pad;         /* snf_vcftext_class, snf_vcftext_flags (SNF_VT_NEW_CHROM: CHROM differs, byte for byte, from the record line in front) */
+} snf_vcftext_line_t;
+
+typedef struct snf_vcftext_table {
+  int64_t n_lines, text_len;
+  const snf_vcftext_line_t* line;   /* host, n_lines */
+  float ms_lines, ms_parse;         /* HIP events around vt_lines + scan, and around vt_parse + vt_chrom */
+} snf_vcftext_table_t;
+
+typedef struct snf_vcftext_pool {
+  int64_t n;
+  const uint8_t* pool;              /* host: the rows one behind the other */
+  const int64_t* off;               /* host, n + 1 */
+  float ms_kernel, _pad;
+} snf_vcftext_pool_t;
+
+typedef struct snf_vcftext snf_vcftext_t;
+/* `capacity`: bytes of text the handle will hold; "target VCF of <capacity> bytes does not fit device <device>" when they cannot be allocated. */
+int snf_vcftext_create(int device, int64_t capacity, snf_vcftext_t** out);
+/* Both append, as snf_fasta_load_text / snf_fasta_load_bgzf do (the same route: bgzf_inflate_wave writes at text + out_off). */
+int snf_vcftext_load_text(snf_vcftext_t* t, const uint8_t* bytes, int64_t len);
+int snf_vcftext_load_bgzf(snf_vcftext_t* t, const uint8_t* compressed, int64_t compressed_len, const snf_bgzf_member_t* members,
+                          int64_t n_members, float* ms_inflate);
+/* Line table and columns of every line; the table stays on the device for snf_vcftext_rewrite. */
+int snf_vcftext_parse(snf_vcftext_t* t, int32_t max_grid, snf_vcftext_table_t* out);
+/* `n` spans [off, off + len) of the text, one behind the other. */
+int snf_vcftext_gather(snf_vcftext_t* t, int64_t n, const int64_t* off, const int64_t* len, int32_t max_grid, snf_vcftext_pool_t* out);
+/* Per row: the bytes [start, start + cut8) of line `line[r]` (0-based; -1: an empty row, the caller writes it) and suffix number
+ * `suffix_id[r]` of the table (suffix_pool, suffix_off[n_suffix + 1]).  Needs a snf_vcftext_parse; rows of lines that are not
+ * SNF_VT_RECORD are refused. */
+int snf_vcftext_rewrite(snf_vcftext_t* t, int64_t n_rows, const int64_t* line, const int32_t* suffix_id, int64_t n_suffix,
+                        const uint8_t* suffix_pool, const int64_t* suffix_off, int32_t max_grid, snf_vcftext_pool_t* out);
+void snf_vcftext_destroy(snf_vcftext_t* t);
+const char* snf_vcftext_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

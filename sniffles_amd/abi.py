@@ -527,6 +527,23 @@ class snf_fasta_fetch_t(C.Structure):
                 ("n_count", C.POINTER(C.c_int32)), ("ms_kernel", C.c_float), ("_pad", C.c_float)]
 
 
+# ---- target VCF on the device (snf_vcftext_*, csrc/snf_vcftext.h)
+VT_HOST, VT_HEADER, VT_RECORD = 0, 1, 2
+VT_BND_FIRST, VT_BND_REVERSE, VT_NEW_CHROM = 1, 2, 4
+VCFTEXT_LINE_DTYPE = np.dtype([(n, "<i8") for n in ("start", "pos", "svlen", "end", "mate_pos")] +
+                              [(n, "<u4") for n in ("send", "cut8", "chrom_end", "span_a", "span_len")] +
+                              [("svtype", "i1"), ("cls", "u1"), ("flags", "u1"), ("_pad", "u1")])
+assert VCFTEXT_LINE_DTYPE.itemsize == 64
+
+
+class snf_vcftext_table_t(C.Structure):
+    _fields_ = [("n_lines", i64), ("text_len", i64), ("line", C.c_void_p), ("ms_lines", C.c_float), ("ms_parse", C.c_float)]
+
+
+class snf_vcftext_pool_t(C.Structure):
+    _fields_ = [("n", i64), ("pool", u8p), ("off", C.POINTER(C.c_int64)), ("ms_kernel", C.c_float), ("_pad", C.c_float)]
+
+
 def extract_config_struct(cfg) -> snf_extract_config_t:
     """`cfg`: anything with the SnifflesConfig attribute names extraction reads (config.py:190-215, 507-617)."""
     g = lambda name, default: getattr(cfg, name, default)

@@ -2073,9 +2073,9 @@ unsigned fa_grid(int64_t items, const FastaKnobs& k) { return (unsigned)std::max
 
 void fa_events(snf_fasta* f) { for (hipEvent_t& e : f->ev) if (!e) SNF_HIP(hipEventCreate(&e)); }
 
-void fa_room(snf_fasta* f, int64_t more) {
+void fa_room(snf_fasta* f, int64_t more, const char* who = "snf_fasta") {      // (`who`: the handle the buffer serves - snf_vcftext holds one too)
   if (more < 0 || f->len + more > f->cap)
-    snf::fail("snf_fasta: " + std::to_string((long long)more) + " more bytes behind " + std::to_string((long long)f->len) + " do not fit the " +
+    snf::fail(std::string(who) + ": " + std::to_string((long long)more) + " more bytes behind " + std::to_string((long long)f->len) + " do not fit the " +
               std::to_string((long long)f->cap) + " bytes the handle was created for");
 }
 void fa_appended(snf_fasta* f, int64_t more) {
@@ -2084,8 +2084,8 @@ void fa_appended(snf_fasta* f, int64_t more) {
   f->have_index = false;
 }
 
-void do_fasta_load_bgzf(snf_fasta* f, const uint8_t* comp, int64_t comp_len, const snf_bgzf_member_t* mem, int64_t n_mem, float* ms) {
-  if (comp_len < 0 || n_mem < 0 || (comp_len && !comp) || (n_mem && !mem)) snf::fail("snf_fasta_load_bgzf: null argument");
+void do_fasta_load_bgzf(snf_fasta* f, const uint8_t* comp, int64_t comp_len, const snf_bgzf_member_t* mem, int64_t n_mem, float* ms, const char* who = "snf_fasta") {
+  if (comp_len < 0 || n_mem < 0 || (comp_len && !comp) || (n_mem && !mem)) snf::fail(std::string(who) + "_load_bgzf: null argument");
   int64_t total = 0;
   std::vector<snf_bgzf_member_t> abs((size_t)n_mem);
   for (int64_t m = 0; m < n_mem; m++) {
@@ -2096,7 +2096,7 @@ void do_fasta_load_bgzf(snf_fasta* f, const uint8_t* comp, int64_t comp_len, con
     abs[(size_t)m] = b; abs[(size_t)m].out_off = f->len + total;      // the kernel writes at text + out_off: the run is appended
     total += b.isize;
   }
-  fa_room(f, total);
+  fa_room(f, total, who);
   const BgzfKnobs k;
   x_release(f->tmp);
   uint8_t* d_comp = x_up(f->tmp, comp, (size_t)comp_len, 16);
@@ -2355,5 +2355,214 @@ void snf_fasta_destroy(snf_fasta_t* f) {
   if (f->d_text) (void)hipFree(f->d_text);
   for (hipEvent_t e : f->ev) if (e) (void)hipEventDestroy(e);
   delete f;
+}
+}
+
+// ================================================================================ target VCF in HBM: host side ====
+#include "snf_vcftext.h"
+
+struct snf_vcftext {
+  snf_fasta fa;                                            // the text buffer and its loaders are the FASTA's (do_fasta_load_bgzf appends into it)
+  snf_vcftext_line_t* d_line = nullptr; int64_t n_lines = -1;      // the line table stays resident for the rewrite
+  std::vector<snf_vcftext_line_t> h_line;
+  std::vector<uint8_t> h_pool; std::vector<int64_t> h_off;
+};
+
+namespace {
+thread_local std::string g_verr;
+
+unsigned vt_grid(int64_t items, int32_t max_grid) {
+  const int64_t cap = max_grid > 0 ? max_grid : (1 << 20);
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, cap));
+}
+
+void vt_drop_table(snf_vcftext* t) {
+  if (t->d_line) { x_free(t->d_line); t->d_line = nullptr; }
+  t->n_lines = -1;
+}
+
+void do_vcftext_parse(snf_vcftext* t, int32_t max_grid, snf_vcftext_table_t* out) {
+  if (!out) snf::fail("snf_vcftext_parse: null argument");
+  snf_fasta* f = &t->fa;
+  vt_drop_table(t);
+  x_release(f->tmp);
+  std::vector<void*>& pool = f->tmp;
+  const int64_t n = f->len, n_chunks = (n + VT_CHUNK - 1) / VT_CHUNK;
+  const size_t N1 = (size_t)n_chunks + 1;
+  VtLinesView lv{};
+  lv.text = f->d_text; lv.n = n; lv.n_chunks = n_chunks;
+  lv.c_ls = x_alloc<uint32_t>(pool, N1);
+  int64_t* p_ls = x_alloc<int64_t>(pool, N1);
+  lv.p_ls = p_ls;
+  SNF_HIP(hipMemset(lv.c_ls + n_chunks, 0, 4));
+  size_t need = 0;
+  SNF_HIP(rocprim::exclusive_scan(nullptr, need, (const uint32_t*)nullptr, (int64_t*)nullptr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  void* scan_tmp = x_alloc<uint8_t>(pool, need);
+  fa_events(f);
+  hipEvent_t ev2 = nullptr;
+  SNF_HIP(hipEventCreate(&ev2));
+  snf_vcftext_table_t r{};
+  try {
+    const unsigned grid = vt_grid(n_chunks, max_grid);
+    SNF_HIP(hipEventRecord(f->ev[0], 0));
+    if (n_chunks) { hipLaunchKernelGGL(vt_lines<false>, dim3(grid), dim3(VT_WG), 0, 0, lv); SNF_HIP(hipGetLastError()); }
+    SNF_HIP(rocprim::exclusive_scan(scan_tmp, need, (const uint32_t*)lv.c_ls, p_ls, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+    int64_t n_lines = 0;
+    x_d2h(&n_lines, p_ls + n_chunks, 8);
+    if (n_lines < 0 || n_lines > n) snf::fail("snf_vcftext_parse: line count out of range");
+    lv.line_start = x_alloc<int64_t>(pool, (size_t)n_lines + 1); lv.n_lines = n_lines;
+    x_h2d(lv.line_start + n_lines, &n, 8);
+    if (n_lines) { hipLaunchKernelGGL(vt_lines<true>, dim3(grid), dim3(VT_WG), 0, 0, lv); SNF_HIP(hipGetLastError()); }
+    SNF_HIP(hipEventRecord(f->ev[1], 0));
+    void* dl = nullptr;
+    const size_t lbytes = ((size_t)n_lines + 1) * sizeof(snf_vcftext_line_t);
+    if (hipMalloc(&dl, lbytes) != hipSuccess) {
+      (void)hipGetLastError();
+      snf::fail("line table of " + std::to_string(lbytes) + " bytes does not fit device " + std::to_string(f->device));
+    }
+    t->d_line = (snf_vcftext_line_t*)dl;
+    VtParseView pv{f->d_text, n, lv.line_start, t->d_line, n_lines};
+    if (n_lines) {
+      hipLaunchKernelGGL(vt_parse, dim3(vt_grid(n_lines, max_grid)), dim3(64), 0, 0, pv); SNF_HIP(hipGetLastError());
+      hipLaunchKernelGGL(vt_chrom, dim3(vt_grid((n_lines + VT_CHROM_WG - 1) / VT_CHROM_WG, max_grid)), dim3(VT_CHROM_WG), 0, 0, pv); SNF_HIP(hipGetLastError());
+    }
+    SNF_HIP(hipEventRecord(ev2, 0));
+    t->h_line.assign((size_t)n_lines + 1, snf_vcftext_line_t{});
+    x_d2h(t->h_line.data(), t->d_line, (size_t)n_lines * sizeof(snf_vcftext_line_t));
+    SNF_HIP(hipDeviceSynchronize());
+    SNF_HIP(hipEventElapsedTime(&r.ms_lines, f->ev[0], f->ev[1]));
+    SNF_HIP(hipEventElapsedTime(&r.ms_parse, f->ev[1], ev2));
+    t->n_lines = n_lines;
+    r.n_lines = n_lines; r.text_len = n; r.line = t->h_line.data();
+  } catch (...) {
+    (void)hipEventDestroy(ev2);
+    x_release(pool);
+    vt_drop_table(t);
+    throw;
+  }
+  (void)hipEventDestroy(ev2);
+  x_release(pool);
+  *out = r;
+}
+
+// the scan over the row sizes, the copy and the way back - what gather and rewrite share
+template <bool REWRITE>
+void vt_rows_out(snf_vcftext* t, VtCopyView v, int32_t max_grid, snf_vcftext_pool_t* out) {
+  snf_fasta* f = &t->fa;
+  std::vector<void*>& pool = f->tmp;
+  const int64_t n = v.n;
+  const size_t N1 = (size_t)n + 1;
+  v.size = x_alloc<int64_t>(pool, N1);
+  int64_t* d_off = x_alloc<int64_t>(pool, N1);
+  SNF_HIP(hipMemset(v.size + n, 0, 8));
+  size_t need = 0;
+  SNF_HIP(rocprim::exclusive_scan(nullptr, need, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  void* scan_tmp = x_alloc<uint8_t>(pool, need);
+  fa_events(f);
+  SNF_HIP(hipEventRecord(f->ev[0], 0));
+  if (n) { hipLaunchKernelGGL(vt_size<REWRITE>, dim3(vt_grid((n + VT_CHROM_WG - 1) / VT_CHROM_WG, max_grid)), dim3(VT_CHROM_WG), 0, 0, v); SNF_HIP(hipGetLastError()); }
+  SNF_HIP(rocprim::exclusive_scan(scan_tmp, need, (const int64_t*)v.size, d_off, (int64_t)0, N1, rocprim::plus<int64_t>(), 0));
+  t->h_off.assign(N1, 0);
+  x_d2h(t->h_off.data(), d_off, N1 * 8);
+  const int64_t total = t->h_off[(size_t)n];
+  if (total < 0) snf::fail("snf_vcftext: row sizes out of range");
+  v.out_off = d_off; v.out = x_alloc<uint8_t>(pool, (size_t)total, 16);
+  if (n && total) { hipLaunchKernelGGL(vt_copy<REWRITE>, dim3(vt_grid(n, max_grid)), dim3(64), 0, 0, v); SNF_HIP(hipGetLastError()); }
+  SNF_HIP(hipEventRecord(f->ev[1], 0));
+  t->h_pool.resize((size_t)total + 1);
+  x_d2h(t->h_pool.data(), v.out, (size_t)total);
+  SNF_HIP(hipDeviceSynchronize());
+  snf_vcftext_pool_t r{};
+  SNF_HIP(hipEventElapsedTime(&r.ms_kernel, f->ev[0], f->ev[1]));
+  r.n = n; r.pool = t->h_pool.data(); r.off = t->h_off.data();
+  x_release(pool);
+  *out = r;
+}
+
+void do_vcftext_gather(snf_vcftext* t, int64_t n, const int64_t* off, const int64_t* len, int32_t max_grid, snf_vcftext_pool_t* out) {
+  if (!out || n < 0 || (n && (!off || !len))) snf::fail("snf_vcftext_gather: null argument");
+  snf_fasta* f = &t->fa;
+  for (int64_t r = 0; r < n; r++)
+    if (off[r] < 0 || len[r] < 0 || off[r] > f->len || len[r] > f->len - off[r]) snf::fail("snf_vcftext_gather: span " + std::to_string((long long)r) + " outside the text");
+  x_release(f->tmp);
+  VtCopyView v{};
+  v.text = f->d_text; v.n = n;
+  v.row_off = x_up(f->tmp, off, (size_t)n); v.row_len = x_up(f->tmp, len, (size_t)n);
+  try { vt_rows_out<false>(t, v, max_grid, out); } catch (...) { x_release(f->tmp); throw; }
+}
+
+void do_vcftext_rewrite(snf_vcftext* t, int64_t n, const int64_t* line, const int32_t* sid, int64_t n_suffix, const uint8_t* spool, const int64_t* soff,
+                        int32_t max_grid, snf_vcftext_pool_t* out) {
+  if (!out || n < 0 || n_suffix < 0 || (n && (!line || !sid)) || !soff) snf::fail("snf_vcftext_rewrite: null argument");
+  if (t->n_lines < 0) snf::fail("snf_vcftext_rewrite before a successful snf_vcftext_parse");
+  if (soff[0] != 0) snf::fail("snf_vcftext_rewrite: suffix_off[0] is not 0");
+  for (int64_t s = 0; s < n_suffix; s++) if (soff[s + 1] < soff[s]) snf::fail("snf_vcftext_rewrite: suffix_off decreases");
+  if (soff[n_suffix] && !spool) snf::fail("snf_vcftext_rewrite: null argument");
+  for (int64_t r = 0; r < n; r++) {
+    if (line[r] < -1 || line[r] >= t->n_lines) snf::fail("snf_vcftext_rewrite: row " + std::to_string((long long)r) + ": no such line");
+    if (line[r] < 0) continue;
+    if (t->h_line[(size_t)line[r]].cls != SNF_VT_RECORD) snf::fail("snf_vcftext_rewrite: row " + std::to_string((long long)r) + ": line " + std::to_string((long long)line[r] + 1) + " was not parsed on the device");
+    if (sid[r] < 0 || sid[r] >= n_suffix) snf::fail("snf_vcftext_rewrite: row " + std::to_string((long long)r) + ": no such suffix");
+  }
+  snf_fasta* f = &t->fa;
+  x_release(f->tmp);
+  VtCopyView v{};
+  v.text = f->d_text; v.n = n; v.line = t->d_line; v.n_lines = t->n_lines;
+  v.row_line = x_up(f->tmp, line, (size_t)n); v.row_suffix = x_up(f->tmp, sid, (size_t)n);
+  v.suffix = x_up(f->tmp, spool, (size_t)soff[n_suffix]); v.suffix_off = x_up(f->tmp, soff, (size_t)n_suffix + 1);
+  try { vt_rows_out<true>(t, v, max_grid, out); } catch (...) { x_release(f->tmp); throw; }
+}
+}  // namespace
+
+#define V_TRY(stmt)                                                    \
+  if (!t) { g_verr = "null handle"; return 1; }                        \
+  if (hipSetDevice(t->fa.device) != hipSuccess) { g_verr = "hipSetDevice failed"; return 1; } \
+  try { stmt; }                                                        \
+  catch (const snf::Error& e) { g_verr = e.msg; return 1; }            \
+  catch (const std::exception& e) { g_verr = e.what(); return 1; }     \
+  return 0;
+
+extern "C" {
+const char* snf_vcftext_last_error(void) { return g_verr.c_str(); }
+int snf_vcftext_create(int device, int64_t capacity, snf_vcftext_t** out) {
+  if (!out || capacity < 0) { g_verr = "snf_vcftext_create: null argument"; return 1; }
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { g_verr = "no HIP device: the target-text kernels need a gfx950 GPU (there is no CPU fallback)"; return 1; }
+  if (device < 0 || device >= nd) { g_verr = "device index out of range"; return 1; }
+  if (hipSetDevice(device) != hipSuccess) { g_verr = "hipSetDevice failed"; return 1; }
+  void* p = nullptr;
+  if (hipMalloc(&p, (size_t)capacity + 64) != hipSuccess) {
+    (void)hipGetLastError();
+    g_verr = "target VCF of " + std::to_string((long long)capacity) + " bytes does not fit device " + std::to_string(device);
+    return 1;
+  }
+  if (hipMemset(p, 0, (size_t)capacity + 64) != hipSuccess) { (void)hipFree(p); g_verr = "hipMemset failed"; return 1; }
+  snf_vcftext* t = new snf_vcftext();
+  t->fa.device = device; t->fa.d_text = (uint8_t*)p; t->fa.cap = capacity;
+  *out = t;
+  return 0;
+}
+int snf_vcftext_load_text(snf_vcftext_t* t, const uint8_t* bytes, int64_t len) {
+  V_TRY(if (len < 0 || (len && !bytes)) snf::fail("snf_vcftext_load_text: null argument");
+        vt_drop_table(t); fa_room(&t->fa, len, "snf_vcftext"); x_h2d(t->fa.d_text + t->fa.len, bytes, (size_t)len); fa_appended(&t->fa, len))
+}
+int snf_vcftext_load_bgzf(snf_vcftext_t* t, const uint8_t* compressed, int64_t compressed_len, const snf_bgzf_member_t* members, int64_t n_members, float* ms_inflate) {
+  V_TRY(vt_drop_table(t); do_fasta_load_bgzf(&t->fa, compressed, compressed_len, members, n_members, ms_inflate, "snf_vcftext"))
+}
+int snf_vcftext_parse(snf_vcftext_t* t, int32_t max_grid, snf_vcftext_table_t* out) { V_TRY(do_vcftext_parse(t, max_grid, out)) }
+int snf_vcftext_gather(snf_vcftext_t* t, int64_t n, const int64_t* off, const int64_t* len, int32_t max_grid, snf_vcftext_pool_t* out) {
+  V_TRY(do_vcftext_gather(t, n, off, len, max_grid, out))
+}
+int snf_vcftext_rewrite(snf_vcftext_t* t, int64_t n_rows, const int64_t* line, const int32_t* suffix_id, int64_t n_suffix, const uint8_t* suffix_pool,
+                        const int64_t* suffix_off, int32_t max_grid, snf_vcftext_pool_t* out) {
+  V_TRY(do_vcftext_rewrite(t, n_rows, line, suffix_id, n_suffix, suffix_pool, suffix_off, max_grid, out))
+}
+void snf_vcftext_destroy(snf_vcftext_t* t) {
+  if (!t) return;
+  vt_drop_table(t);
+  x_release(t->fa.tmp);
+  if (t->fa.d_text) (void)hipFree(t->fa.d_text);
+  for (hipEvent_t e : t->fa.ev) if (e) (void)hipEventDestroy(e);
+  delete t;
 }
 }

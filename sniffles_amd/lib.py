@@ -137,6 +137,17 @@ def bind(lib: C.CDLL) -> C.CDLL:
     for f in ("snf_fasta_create", "snf_fasta_load_text", "snf_fasta_load_bgzf", "snf_fasta_index", "snf_fasta_set_index", "snf_fasta_nruns",
               "snf_fasta_fetch", "snf_fasta_read_text"):
         getattr(lib, f).restype = C.c_int
+    lib.snf_vcftext_create.argtypes = [C.c_int, i64, C.POINTER(vp)]
+    lib.snf_vcftext_load_text.argtypes = [vp, C.c_void_p, i64]
+    lib.snf_vcftext_load_bgzf.argtypes = [vp, C.c_void_p, i64, C.c_void_p, i64, C.POINTER(C.c_float)]
+    lib.snf_vcftext_parse.argtypes = [vp, C.c_int32, C.POINTER(abi.snf_vcftext_table_t)]
+    lib.snf_vcftext_gather.argtypes = [vp, i64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.snf_vcftext_pool_t)]
+    lib.snf_vcftext_rewrite.argtypes = [vp, i64, C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(abi.snf_vcftext_pool_t)]
+    lib.snf_vcftext_destroy.argtypes = [vp]
+    lib.snf_vcftext_destroy.restype = None
+    lib.snf_vcftext_last_error.restype = C.c_char_p
+    for f in ("snf_vcftext_create", "snf_vcftext_load_text", "snf_vcftext_load_bgzf", "snf_vcftext_parse", "snf_vcftext_gather", "snf_vcftext_rewrite"):
+        getattr(lib, f).restype = C.c_int
     lib.snf_batch_pass.argtypes = [vp]
     lib.snf_batch_open.argtypes = [C.POINTER(abi.snf_config_t), C.c_int, C.POINTER(abi.snf_task_input_t), C.c_int32, C.c_int, C.POINTER(vp)]
     for f in ("snf_batch_open", "snf_batch_pass", "snf_batch_create", "snf_batch_add_task", "snf_batch_upload", "snf_batch_call_candidates",
@@ -634,3 +645,133 @@ def genotype_batch(cfg, records: np.ndarray, device: int = 0) -> np.ndarray:
     cs = abi.config_struct(cfg)
     _check(lib, lib.snf_genotype_batch(C.byref(cs), device, records.ctypes.data_as(C.POINTER(abi.snf_call_t)), len(records)))
     return records
+
+
+class VcfText:
+    """A target VCF whose text lives in HBM (one `snf_vcftext_t`, csrc/snf_vcftext.h): `data` - the file's bytes - goes up as it is,
+    as its BGZF members (first member BGZF: inflated on the device, run by run, the route `fasta.DeviceFasta` takes) or inflated on
+    the host (any other gzip).  `parse` gives the line table, `gather` spans of the text, `rewrite` the genotyped lines.
+    `max_grid` (0: uncapped) caps the grids of every kernel: a test hook, as in `genotype_match_batch`."""
+
+    def __init__(self, data: bytes, device: int = 0, run_bytes: int = 256 << 20, max_grid: int = 0):
+        import gzip
+
+        from . import bam
+        from .fasta import _is_bgzf
+        self.lib, self.device, self.max_grid = load(), device, int(max_grid)
+        self._h = C.c_void_p()
+        self.timing = dict(inflate_ms=0.0, lines_ms=0.0, parse_ms=0.0, runs=0)
+        data = bytes(data)
+        gz = data[:2] == b"\x1f\x8b"
+        bgzf = gz and _is_bgzf(data[:65536])
+        mem = None
+        if bgzf:
+            mem = bam.bgzf_members(data)
+            total = int(mem["isize"].sum())
+        elif gz:
+            data = gzip.decompress(data)
+            total = len(data)
+        else:
+            total = len(data)
+        if self.lib.snf_vcftext_create(device, total, C.byref(self._h)) != 0:
+            self._h = C.c_void_p()
+            self._raise()
+        try:
+            buf = np.frombuffer(data, np.uint8)
+            if bgzf:
+                k, n_mem = 0, int(mem.shape[0])
+                ends = mem["payload_off"] + mem["payload_len"].astype(np.int64)
+                while k < n_mem:
+                    j = k + 1
+                    lo = int(mem["payload_off"][k])
+                    while j < n_mem and int(ends[j]) - lo <= int(run_bytes):
+                        j += 1
+                    run = np.ascontiguousarray(mem[k:j]).copy()
+                    hi = int(run["payload_off"][-1]) + int(run["payload_len"][-1])
+                    run["payload_off"] -= lo
+                    run["out_off"] -= run["out_off"][0]
+                    piece = buf[lo:hi]
+                    ms = C.c_float()
+                    self._check(self.lib.snf_vcftext_load_bgzf(self._h, piece.ctypes.data if piece.shape[0] else None, int(piece.shape[0]),
+                                                               run.ctypes.data, int(run.shape[0]), C.byref(ms)))
+                    self.timing["inflate_ms"] += float(ms.value)
+                    self.timing["runs"] += 1
+                    k = j
+            else:
+                self._check(self.lib.snf_vcftext_load_text(self._h, buf.ctypes.data if total else None, total))
+                self.timing["runs"] = 1
+            self.text_len = total
+        except Exception:
+            self.close()
+            raise
+
+    def _raise(self):
+        raise SnifflesAmdError(self.lib.snf_vcftext_last_error().decode("utf-8", "replace"))
+
+    def _check(self, rc):
+        if rc != 0:
+            self._raise()
+
+    def parse(self) -> np.ndarray:
+        """One `abi.VCFTEXT_LINE_DTYPE` row per line of the text."""
+        r = abi.snf_vcftext_table_t()
+        self._check(self.lib.snf_vcftext_parse(self._h, self.max_grid, C.byref(r)))
+        self.timing["lines_ms"], self.timing["parse_ms"] = float(r.ms_lines), float(r.ms_parse)
+        n = int(r.n_lines)
+        if not n:
+            return np.zeros(0, abi.VCFTEXT_LINE_DTYPE)
+        raw = np.ctypeslib.as_array(C.cast(r.line, C.POINTER(C.c_uint8)), shape=(n * abi.VCFTEXT_LINE_DTYPE.itemsize,))
+        return raw.view(abi.VCFTEXT_LINE_DTYPE).copy()
+
+    def _pool(self, r):
+        """(the rows as one bytes object - one copy out of the library's buffer -, off int64[n + 1])"""
+        n = int(r.n)
+        off = np.ctypeslib.as_array(r.off, shape=(n + 1,)).copy()
+        total = int(off[-1])
+        return (C.string_at(r.pool, total) if total else b""), off
+
+    def gather(self, off, length):
+        """The spans [off, off + length) of the text: (pool bytes, off int64[n + 1])."""
+        o, ln = np.ascontiguousarray(off, np.int64).reshape(-1), np.ascontiguousarray(length, np.int64).reshape(-1)
+        n = int(o.shape[0])
+        r = abi.snf_vcftext_pool_t()
+        self._check(self.lib.snf_vcftext_gather(self._h, n, o.ctypes.data if n else None, ln.ctypes.data if n else None, self.max_grid, C.byref(r)))
+        self.last_ms = float(r.ms_kernel)
+        return self._pool(r)
+
+    def strings(self, off, length) -> list:
+        """The same spans as a list of bytes."""
+        raw, o = self.gather(off, length)
+        o = o.tolist()
+        return [raw[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+
+    def rewrite(self, line, suffix_id, suffixes):
+        """Per row the first eight columns of line `line[r]` (0-based; -1: an empty row) and `suffixes[suffix_id[r]]` (bytes):
+        (pool bytes, off int64[n + 1])."""
+        ln, sid = np.ascontiguousarray(line, np.int64).reshape(-1), np.ascontiguousarray(suffix_id, np.int32).reshape(-1)
+        n = int(ln.shape[0])
+        soff = np.zeros(len(suffixes) + 1, np.int64)
+        soff[1:] = np.cumsum([len(s) for s in suffixes])
+        spool = np.frombuffer(b"".join(suffixes) or b"\0", np.uint8)
+        r = abi.snf_vcftext_pool_t()
+        self._check(self.lib.snf_vcftext_rewrite(self._h, n, ln.ctypes.data if n else None, sid.ctypes.data if n else None, len(suffixes),
+                                                 spool.ctypes.data, soff.ctypes.data, self.max_grid, C.byref(r)))
+        self.last_ms = float(r.ms_kernel)
+        return self._pool(r)
+
+    def close(self) -> None:
+        if self._h:
+            self.lib.snf_vcftext_destroy(self._h)
+            self._h.value = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()

@@ -15,6 +15,7 @@ progress reporting stay with the reference.
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field
 
 from . import bam, extract, parallel, snf, vcf
@@ -318,24 +319,49 @@ def combine(snf_paths, config, vcf_handle=None, sample_ids=None, device: int = 0
 
 
 def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle, tandem_repeats=None, device: int = 0, reference=None,
-                 objects: bool = True, timing: dict = None) -> int:
+                 objects: bool = True, timing: dict = None, targets_on_device: bool = False) -> int:
     """Force calling (`--genotype-vcf`, sniffles:190-213, 487-560 and `GenotypeTask.execute`): the SVs of the input VCF are
     matched against this sample's candidates contig by contig and written back with the sample's genotype (contig by
     contig, input order within a contig).  Returns the number of records written.
     `objects=False`: the same text without an `SVCall` on either side - the targets are read as column tables
     (`VCF.read_target_table`), the signatures stay in HBM between extraction and pass (no `--regions`), the candidates stay there
     behind the pass, and match, coverage and genotype of every target are formed on the device (`GenotypeTask.execute_records`).
-    `timing`: a dict that receives the seconds spent per stage (read, extract, pass_match, text) and the match chain's kernel ms."""
+    `targets_on_device=True` (with `objects=False`): the target text goes to HBM as well - `vcf_in_handle` is then a path or the file's
+    bytes (plain, bgzip or gzip), its lines are parsed by `VCF.read_target_table_device` and written back by
+    `VCF.rewrite_genotype_device` (csrc/snf_vcftext.h); the same text.
+    `timing`: a dict that receives the seconds spent per stage (read, extract, pass_match, text) and the match chain's kernel ms; with
+    `targets_on_device` also `parse_kernel_ms` (line table + line parser) and `n_host_lines` (lines the host parser took)."""
+    opened = []      # the target text in HBM (targets_on_device): freed whatever the contig loop raises
+    try:
+        return _genotype_vcf(records, config, vcf_in_handle, vcf_out_handle, tandem_repeats, device, reference, objects, timing, targets_on_device, opened)
+    finally:
+        for text in opened:
+            text.close()
+
+
+def _genotype_vcf(records, config, vcf_in_handle, vcf_out_handle, tandem_repeats, device, reference, objects, timing, targets_on_device, opened) -> int:
+    """The body of `genotype_vcf`; `opened` receives every device handle the caller has to close."""
     import time
     config.mode = "genotype_vcf"
+    if targets_on_device:
+        if objects:
+            raise ValueError("genotype_vcf: targets_on_device=True needs objects=False (the object path reads SVCall objects from a handle)")
+        if not isinstance(vcf_in_handle, (str, bytes, bytearray, memoryview, os.PathLike)):
+            raise TypeError("genotype_vcf: with targets_on_device=True the targets are a path or the file's bytes, not an open handle "
+                            f"({type(vcf_in_handle).__name__}): the text goes to the device as one block")
     clock = time.perf_counter
     spent = dict(read=0.0, extract=0.0, pass_match=0.0, text=0.0, match_kernel_ms=0.0)
     t0 = clock()
-    reader = vcf.VCF(config, vcf_in_handle)
+    reader = vcf.VCF(config, None if targets_on_device else vcf_in_handle)
     by_contig = {}
     if objects:
         for target in reader.read_svs_iter():
             by_contig.setdefault(target.contig, []).append(target)
+    elif targets_on_device:
+        by_contig = reader.read_target_table_device(vcf_in_handle, device)
+        opened.extend({id(t["lines"].text): t["lines"].text for t in by_contig.values()}.values())
+        spent["parse_kernel_ms"] = reader.target_timing["lines_ms"] + reader.target_timing["parse_ms"]
+        spent["n_host_lines"] = reader.n_host_lines
     else:
         by_contig = reader.read_target_table()
     spent["read"] += clock() - t0
@@ -393,7 +419,12 @@ def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle,
                     table = dict(svtype=np.zeros(0, np.int32), pos=np.zeros(0, np.int64), svlen=np.zeros(0, np.int64), mate_contig=np.zeros(0, np.int32),
                                  bnd_is_first=np.zeros(0, np.uint8), cov=np.zeros((0, 5), np.int32), lines=[], mate_names=[])
                 res = task.execute_records(table)
-                tuples = task.genotype_tuples(res) if res is not None else []
+                if targets_on_device:      # (the writer formats the distinct genotype rows, once each; their tuples are read while the task lives)
+                    if res is not None:
+                        uniq, inverse = vcf._distinct_rows(res["gt"])
+                        distinct = (task.genotype_tuples({"gt": uniq}), inverse)
+                else:
+                    tuples = task.genotype_tuples(res) if res is not None else []
                 if res is not None:
                     spent["match_kernel_ms"] += res["kernel_ms"]
         finally:
@@ -407,6 +438,8 @@ def genotype_vcf(records: bam.BamRecords, config, vcf_in_handle, vcf_out_handle,
             for target in res or []:      # task by task, input order inside a task (GenotypeResult.emit, result.py:118-131);
                 writer.rewrite_genotype(target)      # targets on contigs that are not processed are dropped, like the reference
                 n += 1
+        elif res is not None and targets_on_device:
+            n += writer.rewrite_genotype_device(table["lines"], None, None, distinct=distinct) if len(table["lines"]) else 0
         elif res is not None:
             n += writer.rewrite_genotype_records(table["lines"], tuples)
         spent["text"] += clock() - t0

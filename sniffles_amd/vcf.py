@@ -415,23 +415,31 @@ class VCF:
             bnd = (mate_contig, int(mate_pos), alt[0] == "N", "]" in alt)
         return chrom, pos0, ref, alt, qual, flt, info, svtype, svlen, end, bnd
 
+    @classmethod
+    def _read_target_line(cls, line_index, line):
+        """One line of a target VCF (text or bytes): (its stripped text, None) for a header line, (its stripped text, `_parse_target` of
+        the line) for a record.  A malformed line raises as the reference's reader does."""
+        try:
+            if isinstance(line, bytes):
+                line = line.decode("utf-8")
+            text = line.strip()
+            if text == "":
+                raise IndexError("string index out of range")     # the reference indexes the empty string here
+            if text[0] == "#":
+                return text, None
+            return text, cls._parse_target(line)
+        except Exception as e:
+            raise ValueError(f"Error parsing input VCF: Line {line_index}: {e}") from e     # the reference exits here
+
     def _target_lines(self):
         """(1-based line number, the line, its stripped text) of every record of `self.handle` (text or bytes lines); header lines go
         to `self.header_str`.  A malformed line raises as the reference's reader does; the caller parses inside the same guard."""
         self.header_str = ""
         for line_index, line in enumerate(self.handle, 1):
-            try:
-                if isinstance(line, bytes):
-                    line = line.decode("utf-8")
-                text = line.strip()
-                if text == "":
-                    raise IndexError("string index out of range")     # the reference indexes the empty string here
-                if text[0] == "#":
-                    self.header_str += text + "\n"
-                    continue
-                parsed = self._parse_target(line)
-            except Exception as e:
-                raise ValueError(f"Error parsing input VCF: Line {line_index}: {e}") from e     # the reference exits here
+            text, parsed = self._read_target_line(line_index, line)
+            if parsed is None:
+                self.header_str += text + "\n"
+                continue
             yield line_index, text, parsed
 
     def read_svs_iter(self):
@@ -484,6 +492,123 @@ class VCF:
             t["cov"] = np.zeros((len(t["lines"]), 5), np.int32)
         return rows
 
+    def read_target_table_device(self, source, device: int = 0, max_grid: int = 0, run_bytes: int = 256 << 20) -> dict:
+        """`read_target_table` of `io.BytesIO(<the inflated bytes of source>)` with the text in HBM (csrc/snf_vcftext.h): `source` is a
+        path or the file's bytes - plain, bgzip (inflated on the device) or gzip.  The same keys, dtypes, order and `header_str`; `lines`
+        is a `DeviceTargetLines` (it answers `len()` and `[i]` and fetches the text when asked).  The kernel fills the columns of every
+        line it is certain about; the others (`self.host_lines`, 1-based; `self.n_host_lines` of them) go through `_read_target_line` in
+        file order: the first that raises is the file's first error, the others patch their row or join the header.  The host's part
+        is over runs of equal CHROM (contigs in order of first appearance; a contig that reappears appends), over the BND rows (mate
+        names per contig in order of first appearance) and over the host lines - not over the lines.  `self.target_timing`: the kernels' ms."""
+        import os
+
+        import numpy as np
+
+        from . import abi, lib as L, sv
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            data = bytes(source)
+        elif isinstance(source, (str, os.PathLike)):
+            with open(source, "rb") as f:
+                data = f.read()
+        else:
+            raise TypeError("read_target_table_device takes a path or the file's bytes, not an open handle "
+                            f"({type(source).__name__}): the text goes to the device as one block")
+        text = L.VcfText(data, device, run_bytes, max_grid)
+        try:
+            return self._device_table(text, text.parse(), np, abi, sv)
+        except Exception:
+            text.close()
+            raise
+
+    def _device_table(self, text, tab, np, abi, sv) -> dict:
+        self.header_str = ""
+        self.target_timing = dict(text.timing)
+        cls, start = tab["cls"], tab["start"]
+        raw_len = np.append(start[1:], text.text_len) - start if len(tab) else np.zeros(0, np.int64)
+        host_ids = np.flatnonzero(cls == abi.VT_HOST)
+        self.n_host_lines, self.host_lines = int(len(host_ids)), (host_ids + 1).tolist()
+        host_rows, headers = {}, {}
+        if len(host_ids):
+            for k, raw in zip(host_ids.tolist(), text.strings(start[host_ids], raw_len[host_ids])):
+                stripped, parsed = self._read_target_line(k + 1, raw)
+                if parsed is None:
+                    headers[k] = stripped
+                else:
+                    host_rows[k] = (stripped, parsed)
+        hdr_ids = np.flatnonzero(cls == abi.VT_HEADER)
+        for k, raw in zip(hdr_ids.tolist(), text.strings(start[hdr_ids], tab["send"][hdr_ids])):
+            headers[k] = raw.decode("utf-8")
+        self.header_str = "".join(headers[k] + "\n" for k in sorted(headers))
+        is_row = cls == abi.VT_RECORD
+        if host_rows:
+            is_row = is_row.copy()
+            is_row[list(host_rows)] = True
+        rows = np.flatnonzero(is_row)
+        n = int(len(rows))
+        if n == 0:
+            text.close()
+            return {}
+        r = tab[rows]
+        on_host = r["cls"] != abi.VT_RECORD
+        col = dict(line_index=(rows + 1).astype(np.int64), svtype=r["svtype"].astype(np.int32), pos=r["pos"].astype(np.int64),
+                   svlen=r["svlen"].astype(np.int64), end=r["end"].astype(np.int64), mate_ref_start=r["mate_pos"].astype(np.int64),
+                   bnd_is_first=(r["flags"] & abi.VT_BND_FIRST).astype(np.uint8), bnd_is_reverse=((r["flags"] & abi.VT_BND_REVERSE) >> 1).astype(np.uint8))
+        type_names = np.array(sv.TYPES + [None], object)[col["svtype"]]
+        mate = np.full(n, None, object)
+        chrom = {}                                      # row -> CHROM, for the rows that open a run
+        new_run = (r["flags"] & abi.VT_NEW_CHROM) != 0
+        new_run[0] = True
+        # the spans the table needs as strings, in one fetch: names of other types, mates, the CHROM of every run
+        other = np.flatnonzero(~on_host & (col["svtype"] < 0))
+        bnd = np.flatnonzero(~on_host & (col["svtype"] == sv.TYPES.index("BND")))
+        code = {name: k for k, name in enumerate(sv.TYPES)}
+        host_text = {}
+        for i in np.flatnonzero(on_host).tolist():      # the rows the host parsed: every column from `_parse_target`
+            stripped, (c, pos0, _, _, _, _, _, svtype, svlen, end, b) = host_rows[int(rows[i])]
+            host_text[int(rows[i])] = (stripped, "\t".join(stripped.split("\t")[:8]).encode("utf-8"))      # (and what the rewrite keeps of it)
+            col["svtype"][i], col["pos"][i], col["svlen"][i], col["end"][i] = code.get(svtype, -1), pos0, svlen, end
+            type_names[i] = svtype
+            col["mate_ref_start"][i], col["bnd_is_first"][i], col["bnd_is_reverse"][i] = (0, 0, 0) if b is None else (b[1], int(b[2]), int(b[3]))
+            if b is not None:
+                mate[i] = b[0]
+            chrom[i] = c
+            new_run[i] = True
+            if i + 1 < n:
+                new_run[i + 1] = True
+        opens = np.flatnonzero(new_run & ~on_host)
+        want = np.concatenate([other, bnd, opens])
+        span_off = np.concatenate([r["start"][other] + r["span_a"][other], r["start"][bnd] + r["span_a"][bnd], r["start"][opens]])
+        span_len = np.concatenate([r["span_len"][other], r["span_len"][bnd], r["chrom_end"][opens]]).astype(np.int64)
+        got = [b.decode("utf-8") for b in text.strings(span_off, span_len)] if len(want) else []
+        type_names[other] = got[:len(other)]
+        mate[bnd] = got[len(other):len(other) + len(bnd)]
+        for i, c in zip(opens.tolist(), got[len(other) + len(bnd):]):
+            chrom[i] = c
+        # runs of equal CHROM -> contigs
+        run_at = np.flatnonzero(new_run)
+        run_end = np.append(run_at[1:], n)
+        parts = {}
+        for a, b in zip(run_at.tolist(), run_end.tolist()):
+            parts.setdefault(chrom[a], []).append((a, b))
+        out = {}
+        for c, spans in parts.items():
+            idx = np.arange(spans[0][0], spans[0][1]) if len(spans) == 1 else np.concatenate([np.arange(a, b) for a, b in spans])
+            names, seen = [], {}
+            mate_contig = np.full(len(idx), -1, np.int32)
+            m = mate[idx]
+            for j in np.flatnonzero(m != None).tolist():  # noqa: E711 - elementwise
+                k = seen.get(m[j])
+                if k is None:
+                    k = seen[m[j]] = len(names)
+                    names.append(m[j])
+                mate_contig[j] = k
+            out[c] = dict(line_index=col["line_index"][idx], svtype=col["svtype"][idx], svtype_names=type_names[idx].tolist(), pos=col["pos"][idx],
+                          svlen=col["svlen"][idx], end=col["end"][idx], mate_contig=mate_contig, mate_ref_start=col["mate_ref_start"][idx],
+                          bnd_is_first=col["bnd_is_first"][idx], bnd_is_reverse=col["bnd_is_reverse"][idx],
+                          lines=DeviceTargetLines(text, rows[idx], r["start"][idx], r["send"][idx].astype(np.int64), host_text), mate_names=names,
+                          cov=np.zeros((len(idx), 5), np.int32))
+        return out
+
     @staticmethod
     def select_targets(table: dict, keep) -> dict:
         """The rows `keep` (boolean mask or indices) of one contig's target table, order kept."""
@@ -534,3 +659,138 @@ class VCF:
         if out:
             self.handle.write("".join(out))
         return len(out) // 4
+
+    def rewrite_genotype_device(self, lines_obj, rows, gt, tuples=None, max_grid: int = None, distinct=None) -> int:
+        """`rewrite_genotype_records(lines, genotypes)` for the `DeviceTargetLines` of a contig, assembled where the text lies: `rows`
+        selects and orders the lines (indices into `lines_obj`; None: all of them), `gt` is the [n, 8] column of `execute_records` with
+        `tuples` the function that turns such rows into genotype tuples (`lambda g: task.genotype_tuples({"gt": g})`), or the list of
+        tuples itself; `distinct=(tuples of the distinct rows, inverse)` hands over what the caller already worked out (`_distinct_rows`; `gt` is
+        then not read).  The distinct genotypes are formatted once by `format_genotype` and go up as a suffix table; vt_size / vt_copy
+        put the first eight columns of every line in front of its suffix, and one block comes back.  Rows the host parsed are assembled
+        here and spliced in.  The same text, byte for byte.  Returns the number of lines."""
+        import io
+
+        import numpy as np
+        if rows is not None:
+            lines_obj = lines_obj[np.asarray(rows, np.int64)]
+        n = len(lines_obj)
+        fmt, phase = self.config.genotype_format, self.config.phase
+        if distinct is not None:
+            distinct, sid = list(distinct[0]), np.asarray(distinct[1], np.int32).reshape(-1)
+            if len(sid) != n or (n and not (0 <= int(sid.min()) and int(sid.max()) < len(distinct))):
+                raise ValueError(f"rewrite_genotype_device: {n} lines, {len(sid)} genotypes over {len(distinct)} distinct ones")
+            if n == 0:
+                return 0
+        elif tuples is not None:
+            gt = np.asarray(gt).reshape(-1, 8)
+            if len(gt) != n:
+                raise ValueError(f"rewrite_genotype_device: {n} lines, {len(gt)} genotypes")
+            if n == 0:
+                return 0
+            uniq, inverse = _distinct_rows(gt)
+            distinct, sid = tuples(uniq), np.asarray(inverse, np.int32).reshape(-1)
+        else:
+            gt = list(gt)
+            if len(gt) != n:
+                raise ValueError(f"rewrite_genotype_device: {n} lines, {len(gt)} genotypes")
+            if n == 0:
+                return 0
+            seen = {}
+            sid = np.asarray([seen.setdefault(g, len(seen)) for g in gt], np.int32)
+            distinct = list(seen)
+        suffixes = [("\t" + fmt + "\t" + format_genotype(g, phase) + "\n").encode("utf-8") for g in distinct]
+        line = lines_obj.line.copy()
+        on_host = np.isin(line, lines_obj.host_ids) if len(lines_obj.host_ids) else np.zeros(n, bool)
+        line[on_host] = -1
+        text = lines_obj.text
+        if max_grid is not None:
+            keep, text.max_grid = text.max_grid, int(max_grid)
+        try:
+            raw, off = text.rewrite(line, sid, suffixes)
+        finally:
+            if max_grid is not None:
+                text.max_grid = keep
+        self.rewrite_kernel_ms = text.last_ms
+        if on_host.any():
+            pieces, at = [], 0
+            for i in np.flatnonzero(on_host).tolist():
+                pieces.append(raw[at:int(off[i])])
+                at = int(off[i])
+                pieces.append(lines_obj.host_text[int(lines_obj.line[i])][1] + suffixes[int(sid[i])])
+            pieces.append(raw[at:])
+            raw = b"".join(pieces)
+        h = self.handle
+        if isinstance(h, io.TextIOBase):
+            under = getattr(h, "buffer", None)      # a text file over a binary one: the bytes go as they are
+            if under is not None and getattr(h, "encoding", "").lower().replace("-", "") == "utf8":      # (as write_merged does)
+                h.flush()
+                under.write(raw)
+            else:
+                h.write(raw.decode("utf-8"))
+        else:
+            h.write(raw)                            # a binary handle (bgzfout.BgzfWriter / VcfGzWriter take bytes)
+        return n
+
+
+def _distinct_rows(a):
+    """`np.unique(a, axis=0, return_inverse=True)` of an integer table up to the order of the distinct rows: (rows, inverse) with
+    `rows[inverse] == a`.  The row-wise unique sorts records of the row's width (measured on 200 000 x 8: half the time of the whole
+    device text path); here every column is ranked on its own and the ranks are folded into one integer per row - exact, no hashing -
+    as long as the product of the columns' cardinalities fits 62 bits, which genotype rows always do; else the row-wise unique."""
+    import numpy as np
+    a = np.ascontiguousarray(a)
+    if a.ndim != 2 or a.dtype.kind not in "iu" or len(a) == 0:
+        return np.unique(a, axis=0, return_inverse=True)
+    key, radix = np.zeros(len(a), np.int64), 1
+    for j in range(a.shape[1]):
+        vals, code = np.unique(a[:, j], return_inverse=True)
+        if radix * len(vals) >= 1 << 62:
+            return np.unique(a, axis=0, return_inverse=True)
+        key += code.reshape(-1).astype(np.int64) * radix
+        radix *= len(vals)
+    _, first, inverse = np.unique(key, return_index=True, return_inverse=True)
+    return a[first], inverse.reshape(-1)
+
+
+class DeviceTargetLines:
+    """The `lines` column of a target table whose text lives in HBM (`VCF.read_target_table_device`): the handle, the 0-based line of
+    every row and where its stripped text lies.  `len()`, `[i]` (the stripped text, as `read_target_table` keeps it), `[indices]` /
+    `[mask]` / `[slice]` (the same object over those rows: what `VCF.select_targets` asks for) and iteration; the text of the rows is
+    fetched when one of them is asked for, once.  Rows the host parsed carry their text (`host_text`, by line: the stripped text and its
+    first eight columns; one dict for the whole file, so a row is looked up by `np.isin` against `host_ids`, never by a loop over rows).
+    `close()` frees the text in HBM - for every table of the file, they share the handle."""
+
+    def __init__(self, text, line, start, send, host_text, host_ids=None):
+        import numpy as np
+        self.text, self.line, self.start, self.send, self.host_text = text, line, start, send, host_text
+        self.host_ids = np.fromiter(host_text, np.int64, len(host_text)) if host_ids is None else host_ids
+        self._cache = None
+
+    def close(self):
+        self.text.close()
+
+    def __len__(self):
+        return int(len(self.line))
+
+    def _all(self):
+        if self._cache is None:
+            got = [b.decode("utf-8") for b in self.text.strings(self.start, self.send)]
+            if len(self.host_ids):
+                import numpy as np
+                for i in np.flatnonzero(np.isin(self.line, self.host_ids)).tolist():
+                    got[i] = self.host_text[int(self.line[i])][0]
+            self._cache = got
+        return self._cache
+
+    def __getitem__(self, i):
+        import numpy as np
+        if isinstance(i, (int, np.integer)):
+            return self._all()[int(i)]
+        if not isinstance(i, slice):
+            i = np.asarray(i)
+            i = np.flatnonzero(i) if i.dtype == bool else i.astype(np.int64)
+        return DeviceTargetLines(self.text, self.line[i], self.start[i], self.send[i], self.host_text, self.host_ids)
+
+    def __iter__(self):
+        return iter(self._all())
+
