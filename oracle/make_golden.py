@@ -539,13 +539,44 @@ def main_genotype_edges():
         fh.write(json.dumps(doc, sort_keys=True, separators=(",", ":")).encode())
 
 
+def merge_scan_edges_doc(c):
+    """One directed table of tests/merge_scan_cases.py through the reference's own cluster.resolve: the clusters its merge scan leaves
+    (--dev-no-resplit: every one of them is yielded as it stands; the reads of a table are all different, so merge_inner fuses
+    nothing and keeps the list order) - task, svtype, start, end, repeat, long leads, leads - and one hash over the lead order."""
+    import merge_scan_cases as mc
+    import ref_harness as rh
+    from sniffles_amd.soa import SVT, SVTYPES
+    tis = mc.build(c)
+    args = mc.reference_args(c) + ["--dev-no-resplit"]
+    rows, order = [], []
+    for t, ti in enumerate(tis):
+        out = rh.run_reference_clusters(ti, args)
+        for name in SVTYPES:
+            for cl in out.get(name, {}).get("yielded", []):
+                rows.append([t, SVT[name], cl["start"], cl["end"], cl["repeat"], cl["leads_long"] or 0, len(cl["leads"])])
+                order.append([(ld[1], ld[2]) for ld in cl["leads"]])
+    return dict(input_sha=[input_sha(ti) for ti in tis], config=c["cfg"], reference_args=args, clusters=rows,
+                lead_order_sha=hashlib.sha256(repr(order).encode()).hexdigest())
+
+
+def main_merge_scan_edges():
+    """The adaptive merge scan at its edges (tests/test_merge_scan_edges.py): inputs as hashes, the reference's clusters."""
+    import merge_scan_cases as mc
+    doc = {}
+    for name in sorted(mc.CASES):
+        doc[name] = merge_scan_edges_doc(mc.CASES[name])
+        print(f"{name:48s} {len(doc[name]['clusters'])} clusters")
+    with gzip.GzipFile(os.path.join(ROOT, "tests", "golden", "merge_scan_edges.json.gz"), "wb", mtime=0) as fh:
+        fh.write(json.dumps(doc, sort_keys=True, separators=(",", ":")).encode())
+
+
 if __name__ == "__main__":
     # python oracle/make_golden.py                 -> every fixture family
     # python oracle/make_golden.py vcf sample      -> only these families
     # python oracle/make_golden.py main fuzz_4_2   -> single cases of the `main` / `combine` families
     FAMILIES = dict(main=main, clusters=main_clusters, regenotype=main_regenotype, combine=main_combine, consensus=main_consensus, consensus_long=main_consensus_long, consensus_class_edges=main_consensus_class_edges, consensus_thresholds=main_consensus_thresholds, combine_task=main_combine_task,
                     bam=main_bam_fixtures, extract=main_extract, snf=main_snf, vcf=main_vcf, sample=main_sample, genotype=main_genotype, population=main_population, genotype_vcf=main_genotype_vcf,
-                    genotype_edges=main_genotype_edges)
+                    genotype_edges=main_genotype_edges, merge_scan_edges=main_merge_scan_edges)
     argv = sys.argv[1:]
     fams = [a for a in argv if a in FAMILIES] or list(FAMILIES)
     names = set(a for a in argv if a not in FAMILIES)

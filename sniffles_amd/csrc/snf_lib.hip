@@ -736,6 +736,10 @@ void enqueue_keys(snf_batch_impl* b);
 // coverage samples by the thread-per-call kernel d4_coverage instead of d4s_coverage (launch_coverage)
 bool coverage_per_call(const snf_batch_impl* b) { return b->k.d4_thread || !b->v.wave_path; }
 
+// cluster_repeat_h_max as the integer the run cut is resolved from: the conversion of a double beyond int (3e9) or of a NaN is
+// undefined, so such a value is clamped - a run_gap above every distance merely cuts nothing, and the floor of 1000 holds below
+static int gap_int(double x) { return !(x > 0.0) ? 0 : x >= 2147483647.0 ? 2147483647 : (int)x; }
+
 void do_upload(snf_batch_impl* b) {
   SNF_TRACE("snf_batch_upload");
   View& v = b->v;
@@ -745,7 +749,7 @@ void do_upload(snf_batch_impl* b) {
   if (T >= (1 << 16)) fail("too many tasks in one batch (max 65535)");
   if (N >= (int64_t)1 << 31 || R >= (int64_t)1 << 31) fail("batch too large for 32-bit lead/read indices");
   v.cfg = b->cfg; v.T = T; v.N = N; v.R = R; v.NTR = NTR;
-  const int gap_base = b->cfg.cluster_merge_bnd > (int)b->cfg.cluster_repeat_h_max ? b->cfg.cluster_merge_bnd : (int)b->cfg.cluster_repeat_h_max;
+  const int gap_base = b->cfg.cluster_merge_bnd > gap_int(b->cfg.cluster_repeat_h_max) ? b->cfg.cluster_merge_bnd : gap_int(b->cfg.cluster_repeat_h_max);
   v.run_gap = b->k.run_gap != KNOB_UNSET ? b->k.run_gap : (gap_base > 1000 ? gap_base : 1000);
   v.wave_path = b->k.wave_path ? 1 : 0;
   b->fused = b->k.fuse && N <= ((int64_t)1 << 25);
@@ -2158,6 +2162,8 @@ void do_fetch(snf_batch_impl* b, int stage, snf_result_t* out) {
                     "fallback %lld alt bytes %lld fused bytes through the shared counter %llu (the rest in the waves' own slices; the split depends on scheduling, the total and the capacity do not) | ALT lists copy %llu small %llu large %llu/%llu/%llu/%llu thread %llu rows %llu\n", (long long)c.n_valid, (long long)c.n_occ, (long long)c.n_bins, (long long)c.n_seeds, (long long)c.n_clusters,
             (long long)c.n_rc, (long long)c.n_calls, (long long)c.n_cons, (long long)c.n_cons_reads, (long long)c.n_cons_fallback,
             (long long)c.alt_total, c.pool_extra_used, c.n_cls[0], c.n_cls[1], c.n_cls[2], c.n_cls[3], c.n_cls[4], c.n_cls[5], c.n_cls[6], c.n_cls[7]);
+    // the merge scan's own account (both counters start from zero with the rest of Counts: z0_init / enqueue_pass_init)
+    fprintf(stderr, "[SNF_PROF] merge scan: %lld runs, %lld groups redone serially (run_gap %d)\n", (long long)c.n_runs, (long long)c.n_dirty_groups, (int)v.run_gap);
   }
   memcpy(b->r_status.data(), v.res_status, (size_t)T * sizeof(int32_t));
   memcpy(b->r_cov.data(), v.res_cov, (size_t)T * sizeof(double));

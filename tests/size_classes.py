@@ -5,7 +5,8 @@ silently tests the middle of a class is what this module is there to prevent.  e
 kernels and the merge kernel that calls them (tests/ed_edges.py, tests/test_edit_distance_edges.py).  extract_thresholds(): the same
 for the extraction kernels (tests/extract_edges.py, tests/test_extract_edges.py).  coverage_thresholds(): the same for the read-table rank
 index, the coverage kernels on it and the genotype table (tests/coverage_cases.py, tests/test_coverage_edges.py, tests/test_genotype_edges.py).
-window_thresholds(): the same for the window front end and its packed fields (tests/window_cases.py, tests/test_window_edges.py)."""
+window_thresholds(): the same for the window front end and its packed fields (tests/window_cases.py, tests/test_window_edges.py).
+merge_thresholds(): the same for the adaptive merge scan and the rule of its run cut (tests/merge_scan_cases.py, tests/test_merge_scan_edges.py)."""
 import os
 import re
 
@@ -232,6 +233,51 @@ def window_thresholds():
         ("t * 8 + svtype fits the group of whead2", (((1 << t["t_bits"]) - 1) * 8 + 7) <= t["h2_grp_mask"]),
         ("the instances ascend", WAVE == t["win_small"] < t["win_mid"] == WIN_MID < t["win_maxcap"]),
         ("the pad is a power of two that divides a block", t["pad"] & (t["pad"] - 1) == 0 and WAVE % t["pad"] == 0),
+    ]
+    for what, ok in rel:
+        if not ok:
+            raise AssertionError(f"size_classes: {what} - no longer true of the literals as read: {t}")
+    return t
+
+
+def merge_thresholds():
+    """dict of the literals of the adaptive merge scan (snf_stage_cluster.h: compute_metrics, merge_walk, c4_emit) and of the rule
+    that resolves its run cut (snf_lib.hip: do_upload).  The reference's sample cap is written twice (where the leads are read and
+    where the sums are added), the bound of the added sums three times; a copy with another value is an error, like a literal that
+    is no longer found."""
+    c, lib_hip = _src("snf_stage_cluster.h"), _src("snf_lib.hip")
+    cap = _one(r"int64_t n = len < (\d+) \? len : (\d+);", c, "the sample cap of compute_metrics")
+    cap_added = _one(r"const int64_t nn_ = Lm < (\d+) \? Lm : (\d+);", c, "the sample cap of the added sums (merge_walk)")
+    added = _one(r"if \(!v\.merge_reread && Lm < (\d+) && A\.cs\.s2 != ~0ull && B\.cs\.s2 != ~0ull && A\.cs\.hi == B\.lo\) \{", c, "the rule of the added sums")
+    mch = _one(r"constexpr int MCH = (\d+);", c, "MCH")
+    wide = _one(r"wide \|= \(uint64_t\)\(d < 0 \? -d : d\) >> (\d+);", c, "the switch to 128-bit sums")
+    fits = _one(r"const bool fits = S2m < \(\(i128\)1 << (\d+)\) && S1m < \(\(i128\)1 << (\d+)\) && S1m > -\(\(i128\)1 << (\d+)\);", c, "the bound of the added sums")
+    hand = _one(r"if \(hd\.n > (\d+)\) \{ hand_c = ", c, "the hand-over size of c4_emit")
+    cut = _one(r"cut = inner > v\.run_gap;", c, "the run cut of b1_seedmetrics_body")
+    base = _one(r"const int gap_base = b->cfg\.cluster_merge_bnd > gap_int\(b->cfg\.cluster_repeat_h_max\) \? b->cfg\.cluster_merge_bnd : gap_int\(b->cfg\.cluster_repeat_h_max\);",
+                lib_hip, "the base of run_gap (the larger of cluster_merge_bnd and cluster_repeat_h_max)")
+    gap = _one(r"v\.run_gap = b->k\.run_gap != KNOB_UNSET \? b->k\.run_gap : \(gap_base > (\d+) \? gap_base : (\d+)\);", lib_hip, "the floor of run_gap")
+    clamp = _one(r"static int gap_int\(double x\) \{ return !\(x > 0\.0\) \? 0 : x >= (\d+)\.0 \? (\d+) : \(int\)x; \}", lib_hip, "the clamp of run_gap's cast")
+    assert cut and base
+    same = [("the sample cap of compute_metrics", cap[0], cap[1]), ("the sample cap of the added sums", cap_added[0], cap_added[1]),
+            ("the sample cap where the leads are read and where the sums are added", cap[0], cap_added[0]),
+            ("the bound of the added sums", fits[0], fits[1]), ("the bound of the added sums", fits[1], fits[2]),
+            ("the floor of run_gap", gap[0], gap[1]), ("the clamp of run_gap's cast", clamp[0], clamp[1])]
+    for what, a, b in same:
+        if int(a) != int(b):
+            raise AssertionError(f"size_classes: {what} is written as two different numbers ({a}, {b})")
+    t = dict(sample_cap=int(cap[0]), added_below=int(added), mch=int(mch), wide_shift=int(wide), fits_shift=int(fits[0]), run_gap_floor=int(gap[0]),
+             run_gap_max=int(clamp[0]), hand_over=int(hand))
+    rel = [
+        ("the sample cap is the reference's (compute_metrics, max_n = 100)", t["sample_cap"] == REF_METRICS),
+        ("the sums are added below the first length whose step is 2", t["added_below"] == 2 * t["sample_cap"] and t["added_below"] // t["sample_cap"] == 2
+         and (t["added_below"] - 1) // t["sample_cap"] == 1),
+        ("the squares of added_below - 1 deviations below 2^wide_shift stay below the bound of the added sums",
+         (t["added_below"] - 1) * ((1 << t["wide_shift"]) - 1) ** 2 < 1 << t["fits_shift"]),
+        ("... and twice the bound fits int64_t / uint64_t (two parts, each below it, are added before the check)", t["fits_shift"] + 1 <= 63),
+        ("a batch of requests is shorter than the sample cap", 1 < t["mch"] < t["sample_cap"]),
+        ("the clamp of run_gap's cast fits int32_t", t["run_gap_max"] < 1 << 31),
+        ("clusters up to a group of eight stay with d1g_refine<8>", t["hand_over"] == GROUP),
     ]
     for what, ok in rel:
         if not ok:
