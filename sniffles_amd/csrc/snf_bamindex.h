@@ -2,8 +2,8 @@
 // snf_bgzf_inflate: the inflated stream, d_rec_off and the member table; the host adds one column, the file offset of every member.
 //
 // Reference counterpart: the index pysam / htslib require behind `bam.fetch` (sniffles:172 check_index, leadprov.py:488) - htslib's
-// hts_idx_push / bam_endpos / hts_reg2bin; the host form of the same rules is tests/bam_index_cases.py.  Included from snf_extract.hip
-// behind snf_bgzf.h (the lane helpers, x_header and x_load_ops are the extraction's).
+// hts_idx_push / bam_endpos / hts_reg2bin; the host form of the same rules is tests/bam_index_cases.py.  Kernels of
+// snf_container.h: nothing else may include this header (the lane helpers, x_header and x_load_ops are snf_lanes.h's).
 //
 //   bai_span     per record: end (bam_endpos: pos + the summed lengths of M D N = X, pos + 1 when that is zero or the record is flagged
 //                unmapped), bin (reg2bin(pos, end) for min_shift 14 / depth 5, recomputed - the record's own bin field is not read),
@@ -26,6 +26,8 @@
 //                refID << 32 | bin holds it).
 // No kernel here waits for another workgroup: what depends on a predecessor's result (the bin) is a kernel of its own.
 #pragma once
+#include "../../include/sniffles_amd.h"
+#include "snf_lanes.h"
 
 namespace snf {
 

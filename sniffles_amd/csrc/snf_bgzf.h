@@ -1,7 +1,7 @@
 // snf_bgzf.h - the container layer on the GPU: BGZF members -> inflated BAM stream -> record boundaries -> record heads.
 //
 // Reference counterpart: pysam / htslib's BGZF reader and record iterator behind `bam.fetch` (leadprov.py:487); the host form of
-// the same three steps is sniffles_amd/bam.py (bgzf_inflate, parse_bam).  Included from snf_extract.hip (its lane helpers are used).
+// the same three steps is sniffles_amd/bam.py (bgzf_inflate, parse_bam).  Kernels of snf_container.h: nothing else may include this header.
 //
 //   bgzf_inflate_wave   one wave (a 64-thread workgroup) per BGZF member, the grid strides over the members.  RFC 1951 inflate: lane 0
 //                       decodes symbols into a batch of up to 64 tokens (a literal or a (length, distance) pair) through a primary
@@ -23,6 +23,8 @@
 //                       A chain of dependent LDS reads per record; the carries are a chain of dependent L2 round trips per segment.
 //   bam_heads           a thread per record: the first six dwords of the record, then (second launch) its NUL-padded read name.
 #pragma once
+#include "../../include/sniffles_amd.h"
+#include "snf_lanes.h"
 
 namespace snf {
 

@@ -2,7 +2,7 @@
 // BC extra field) -> one contiguous file image.
 //
 // Reference counterpart: pysam.tabix_index / bgzip behind `--vcf out.vcf.gz` (sniffles:573-584: zlib level 6 on one host thread) and
-// gzip.compress in the SNF writer (snf.py:291-298).  Included from snf_extract.hip behind snf_bgzf.h (its lane helpers are used).
+// gzip.compress in the SNF writer (snf.py:291-298).  Kernels of snf_container.h: nothing else may include this header.
 //
 //   deflate_member  one workgroup (DZ_WG threads) per member of at most DZ_MAX input bytes, the grid strides over the members.
 //                   The member's input lives in LDS.
@@ -28,6 +28,7 @@
 //                   No workgroup waits for another; nothing depends on the grid or on the order of lanes.
 //   deflate_pack    the members' slots -> the file image at the offsets of a rocPRIM exclusive scan over the member sizes.
 #pragma once
+#include "snf_lanes.h"
 
 namespace snf {
 

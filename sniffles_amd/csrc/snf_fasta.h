@@ -2,9 +2,9 @@
 // batched base fetches, without the text ever returning to the host.
 //
 // Reference counterpart: pysam.FastaFile behind `_mask_N_coverage` (leadprov.py:420-443) and the VCF writer's REF / ALT resolution
-// (vcf.py:108-120, 302-342); the host form of the same rules is sniffles_amd/fasta.py FastaFile (`_scan_bytes`, `fetch`).  Included
-// from snf_extract.hip behind snf_bgzf.h (the lane helpers are the extraction's; a bgzip reference is inflated by bgzf_inflate_wave
-// straight into the text buffer).
+// (vcf.py:108-120, 302-342); the host form of the same rules is sniffles_amd/fasta.py FastaFile (`_scan_bytes`, `fetch`).  Kernels of
+// snf_container.h: nothing else may include this header (the lane helpers are snf_lanes.h's; a bgzip reference is inflated by
+// snf_bgzf.h's bgzf_inflate_wave straight into the text buffer).
 //
 // The text has at least 16 readable bytes behind it and starts 16-byte aligned.  Text offsets are 64-bit, base coordinates 32-bit.
 // Work is cut alike in fa_index and fa_nruns: a thread takes one aligned FA_VEC-byte word, a wave FA_WAVE_BYTES, a workgroup of FA_WG
@@ -27,6 +27,8 @@
 //              bases go to the pool at off[q], the wave counts its 'N' bytes by ballot.
 // No kernel here waits for another workgroup.  Plain C++ stores only.
 #pragma once
+#include "snf_lanes.h"
+#include "snf_bgzf.h"
 
 namespace snf {
 

@@ -4,8 +4,8 @@
 // Reference counterpart: `VCF.read_svs_iter` / `rewrite_genotype` (vcf.py:352-481); the host form of the same rules is
 // sniffles_amd/vcf.py `_parse_target`, `read_target_table`, `rewrite_genotype_records`, and it stays the judge: a line gets the class
 // VT_RECORD only where the kernel is certain that `_parse_target` would not raise and would give the same values.  Everything else
-// is VT_HOST and goes through the host parser, line by line.  Included from snf_extract.hip behind snf_fasta.h (the lane helpers are the
-// extraction's, the word masks the FASTA's; a bgzip file is inflated by bgzf_inflate_wave straight into the text buffer).
+// is VT_HOST and goes through the host parser, line by line.  Kernels of snf_container.h: nothing else may include this header (the lane helpers
+// are snf_lanes.h's, the word masks snf_fasta.h's; a bgzip file is inflated by bgzf_inflate_wave straight into the text buffer).
 //
 // The text has at least 16 readable bytes behind it and starts 16-byte aligned.  Work is cut as in snf_fasta.h:
 //
@@ -23,6 +23,9 @@
 //   vt_size / vt_copy   the size of every output row (a span of the text, plus a suffix), rocPRIM scans, a wave per row copies.
 // No kernel here waits for another workgroup.  Plain C++ stores only.
 #pragma once
+#include "../../include/sniffles_amd.h"
+#include "snf_lanes.h"
+#include "snf_fasta.h"
 
 namespace snf {
 

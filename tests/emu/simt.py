@@ -1,10 +1,10 @@
 """TEST-ONLY: the gfx950 wave kernels on the host.
 
-tests/emu/emu.py compiles the `SNF_EMU` halves of sniffles_amd/csrc (thread-per-item bodies as serial loops); the wave /
-workgroup kernels (`snf_wave_*.h`) are outside it.  This module compiles them UNCHANGED with g++ against the fibre shim in
-tests/emu/simt/hip/hip_runtime.h (every thread of a workgroup is a cooperative fibre; cross-lane operations, DPP and
-barriers are modelled) so their logic can be checked against the reference's golden vectors without a GPU.  Never
-shipped, never loadable through `sniffles_amd.lib.load()`.
+The one host tier: this module compiles the product's four translation units (sniffles_amd/csrc) UNCHANGED with g++ against
+the fibre shim in tests/emu/simt/hip/hip_runtime.h (every thread of a workgroup is a cooperative fibre; cross-lane
+operations, DPP and barriers are modelled) so every kernel's logic can be checked against the reference's golden vectors
+without a GPU; tests/emu/emu.py hands the same library out under the name the tests import.  Never shipped, never loadable
+through `sniffles_amd.lib.load()`.
 """
 import ctypes as C
 import os
