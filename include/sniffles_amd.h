@@ -336,7 +336,7 @@ int snf_batch_upload(snf_batch_t* b);
  * On failure nothing is left behind (*out = NULL).  The tasks' arrays are borrowed until the call returns. */
 #define SNF_RUN_NONE 0
 #define SNF_RUN_CANDIDATES 1
-#define SNF_RUN_PASS 0x100   /* | SNF_OUT_CANDIDATES or SNF_OUT_EXECUTE (| SNF_OUT_DEVICE) */
+#define SNF_RUN_PASS 0x100   /* | SNF_OUT_CANDIDATES or SNF_OUT_EXECUTE (| SNF_OUT_DEVICE, | SNF_OUT_ALL_CANDIDATES) */
 int snf_batch_open(const snf_config_t* cfg, int device, const snf_task_input_t* tasks, int32_t n_tasks, int run, snf_batch_t** out);
 void snf_batch_destroy(snf_batch_t* b);
 
@@ -367,8 +367,14 @@ int snf_batch_pass(snf_batch_t* batch);
  *                       records, ALT bytes and read names the parent process will see cross PCIe
  *   | SNF_OUT_DEVICE    the result stays in HBM until the fetch (instead of being stored straight into pinned host memory by
  *                       the kernels): required for snf_batch_export_device
+ *   | SNF_OUT_ALL_CANDIDATES   (with SNF_OUT_EXECUTE) the pass forms every candidate, also those the block can never hold.  Without
+ *                       it snf_batch_pass in execute mode with QC on (no config.no_qc, no config.dev_output_candidates) forms no
+ *                       candidate of the single-breakend types, which always fail QC (postprocessing.py:244-246): the block is
+ *                       the same, snf_batch_n_candidates and a stage-0 fetch behind such a pass are without them.  For callers
+ *                       that count the candidates (Task.sv_id of the drop-in CallTask).  The two calls on their own
+ *                       (snf_batch_call_candidates, snf_batch_finalize) always form every candidate.
  * snf_call_t.alt_off / rn_off of the returned records index the returned pools. */
-enum snf_output { SNF_OUT_CANDIDATES = 0, SNF_OUT_EXECUTE = 1, SNF_OUT_DEVICE = 2 };
+enum snf_output { SNF_OUT_CANDIDATES = 0, SNF_OUT_EXECUTE = 1, SNF_OUT_DEVICE = 2, SNF_OUT_ALL_CANDIDATES = 4 };
 int snf_batch_set_output(snf_batch_t* b, int mode);
 
 /* Where the stage-1 result lands on the host: `block` receives [ records | read names ] and `alt` the ALT section, both

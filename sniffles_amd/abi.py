@@ -117,7 +117,7 @@ class snf_export_layout_t(C.Structure):
 
 
 # enum snf_output (snf_batch_set_output)
-OUT_CANDIDATES, OUT_EXECUTE, OUT_DEVICE = 0, 1, 2
+OUT_CANDIDATES, OUT_EXECUTE, OUT_DEVICE, OUT_ALL_CANDIDATES = 0, 1, 2, 4
 
 
 class snf_clusters_t(C.Structure):

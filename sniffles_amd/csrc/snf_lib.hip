@@ -290,7 +290,8 @@ struct snf_batch_impl {
   int64_t pf_words = 0;           // prefilter bitmap size (uint32 words)
   // a whole pass (call_candidates + finalize) as ONE HIP graph per result configuration (snf_batch_pass): captured on the second
   // pass of a configuration - every launch size is known from the first -, replayed afterwards
-  struct PassGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int passes = 0; int rn_state = 0; int rn_defer = 0; size_t cap_out = 0, cap_alt = 0; };
+  struct PassGraph { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int passes = 0; int rn_state = 0; int rn_defer = 0; size_t cap_out = 0, cap_alt = 0;
+                     bool skipped_big[3] = {false, false, false}; };      // (which x_big launches the captured pass left out: the graphs of two output modes may differ in it)
   std::map<std::tuple<void*, void*, int>, PassGraph> graphs;   // key: (result block, ALT block, output mode)
   int graph_mode = 0;             // set at upload: 2 = replay (small batches, or SNF_GRAPH=1), 0 = eager, 1 = replay only while no other batch of
                                   // this process has a pass in flight
@@ -338,8 +339,13 @@ struct snf_batch_impl {
   HostBuf hb_out, hb_alt;            // stage-1 fetch: the output block (snf_stage_out.h), the ALT section
   std::vector<std::pair<void*, size_t>> ext_ranges;   // caller memory page-locked for them (snf_batch_set_result_memory)
   // class sizes of this handle's previous finalize (same input -> same sizes; first pass: one host wait for them)
-  bool have_hist = false; int64_t hist_calls = 0, hist_small = 0, hist_large = 0, hist_copy = 0;
-  bool have_big_hist = false; int64_t hist_big[3] = {0, 0, 0};   // items of the previous whole pass for x_big<0 / 1 / 2> (0: that launch is skipped)
+  // "Same input" holds per skip state only: a pass with View::skip_single forms no single-breakend clusters - fewer calls, and perhaps none
+  // of more than 64 leads where a candidates pass of the same handle has one.  One set per state (hints_of), so that a handle whose
+  // modes alternate skips x_big only on what a pass of the SAME state has seen.
+  struct PassHints {
+    bool have_hist = false; int64_t hist_calls = 0, hist_small = 0, hist_large = 0, hist_copy = 0;
+    bool have_big_hist = false; int64_t hist_big[3] = {0, 0, 0};   // items of the previous whole pass for x_big<0 / 1 / 2> (0: that launch is skipped)
+  } hints[2];                        // [View::skip_single of the candidate stage they were learned from]
   bool skipped_big[3] = {false, false, false};
   int out_mode = 0;                  // enum snf_output
   std::vector<int32_t> r_status; std::vector<int64_t> r_off; std::vector<double> r_cov;
@@ -352,6 +358,8 @@ struct snf_batch_impl {
   struct Ev { hipEvent_t a, b; const char* name; int64_t bytes; };
   std::vector<Ev> evs; size_t ev_used = 0;
 };
+// the hints of the current candidates' skip state (View::skip_single is set before a candidate stage is enqueued and holds until the next)
+inline snf_batch_impl::PassHints& hints_of(snf_batch_impl* b) { return b->hints[b->v.skip_single ? 1 : 0]; }
 
 // ---- device memory ----
 // dalloc_own: one hipMalloc per buffer (growable scratch that is freed and re-allocated: dfree_one).
@@ -1523,7 +1531,7 @@ void enqueue_refine(snf_batch_impl* b) {
     KERNEL_GRID(d1w, grid, dim3(64), v, 0, "d1w_refine", N * 36, heavy);
   if (!(v.wave_path && b->fused)) KERNEL_N(d1_refine, v, N, v.wave_path ? 0 : N * 36, quiet);   // (next to the wave kernels every item would return at once)
   b->skipped_big[0] = b->skipped_big[1] = b->skipped_big[2] = false;
-  if (v.wave_path && b->have_big_hist && b->hist_big[0] == 0) b->skipped_big[0] = true;      // (same input: no cluster of more than 64 leads)
+  if (v.wave_path && hints_of(b).have_big_hist && hints_of(b).hist_big[0] == 0) b->skipped_big[0] = true;      // (same input: no cluster of more than 64 leads)
   else if (v.wave_path) KERNEL_GRID(x_big<0>, dim3(b->slots_big), dim3(64), v, 0, "x_big_refine", 0, heavy);   // clusters of more than 64 leads, one wave each
 }
 // the refined-cluster table, call_from of every refined cluster, the candidates compacted
@@ -1560,7 +1568,7 @@ void enqueue_call(snf_batch_impl* b) {
   } else if (v.wave_path)
     KERNEL_GRID(d2w, grid, dim3(64), v, 0, "d2w_call", N * 32, heavy);
   if (!(v.wave_path && b->fused)) KERNEL_N(d2_call, v, N, v.wave_path ? 0 : N * 32, quiet);
-  if (v.wave_path && b->have_big_hist && b->hist_big[1] == 0) b->skipped_big[1] = true;
+  if (v.wave_path && hints_of(b).have_big_hist && hints_of(b).hist_big[1] == 0) b->skipped_big[1] = true;
   else if (v.wave_path) KERNEL_GRID(x_big<1>, dim3(b->slots_big), dim3(64), v, 0, "x_big_call", 0, heavy);
   if (b->fused && v.chain_on) KERNEL_N(d3cc_compact, v, N, 0, quiet);
   else if (b->fused) KERNEL_N(d3ck_compact, v, N, 0, quiet);      // (the tile sums of cdflag: published where a candidate is written)
@@ -1853,8 +1861,8 @@ void run_finalize(snf_batch_impl* b) {
   // Launch sizes of the data-dependent kernels.  Grids much larger than the work flood the dispatcher with empty workgroups
   // (measured: every co-running kernel of the device slows down), grids smaller make the kernels stride.  A handle that
   // has finalized before knows its sizes (same input); the first pass waits once for the counters d3_taskoff published.
-  int64_t n_calls_hint = b->hist_calls;
-  if (!b->have_hist && NS > 0) {
+  int64_t n_calls_hint = hints_of(b).hist_calls;
+  if (!hints_of(b).have_hist && NS > 0) {
     SNF_HIP(hipEventSynchronize(b->ev_counts));
     n_calls_hint = b->h_cnt->n_calls;
   }
@@ -1871,7 +1879,7 @@ void run_finalize(snf_batch_impl* b) {
       KERNEL_GRID(e1w_finalize<5>, dim3((unsigned)grid), dim3(64), v, 0, "e1w_finalize", 0, heavy);
     }
     if (!v.wave_path) KERNEL_N(e1_finalize, v, NS, 0, quiet);
-    if (v.wave_path && b->have_big_hist && b->hist_big[2] == 0 && b->finalize_runs == 1) b->skipped_big[2] = true;
+    if (v.wave_path && hints_of(b).have_big_hist && hints_of(b).hist_big[2] == 0 && b->finalize_runs == 1) b->skipped_big[2] = true;
     else if (v.wave_path) KERNEL_GRID(x_big<2>, dim3(b->slots_big), dim3(64), v, 0, "x_big_finalize", 0, heavy);
   }
   const bool fast_alt = v.wave_path && b->fused && NS <= ((int64_t)1 << 22) * 256;
@@ -1889,15 +1897,15 @@ void run_finalize(snf_batch_impl* b) {
       enqueue_output_head(b);
       stage_copy_block(b);      // (staged result: the block leaves behind f4w_emit, next to the consensus kernels)
     }
-    if (!b->have_hist) {   // first finalize of this handle: the class sizes e3b has just written, one host wait
+    if (!hints_of(b).have_hist) {   // first finalize of this handle: the class sizes e3b has just written, one host wait
       d2h(b, b->h_cnt, v.cnt, sizeof(Counts));
       dsync(b);
       const Counts& c = *b->h_cnt;
-      b->hist_small = (int64_t)c.n_cls[1]; b->hist_large = (int64_t)(c.n_cls[2] + c.n_cls[3] + c.n_cls[4] + c.n_cls[5]); b->hist_copy = (int64_t)c.n_cls[0];
-      b->hist_calls = c.n_calls; b->have_hist = true;
+      hints_of(b).hist_small = (int64_t)c.n_cls[1]; hints_of(b).hist_large = (int64_t)(c.n_cls[2] + c.n_cls[3] + c.n_cls[4] + c.n_cls[5]); hints_of(b).hist_copy = (int64_t)c.n_cls[0];
+      hints_of(b).hist_calls = c.n_calls; hints_of(b).have_hist = true;
     }
     join_fuse_copy(b);          // (the consensus kernels and e4c_copy read the fused bytes; e2a / e3b above only offsets and lengths)
-    enqueue_consensus_wave(b, b->hist_small + 1, b->hist_large + 1, b->hist_copy + 1);
+    enqueue_consensus_wave(b, hints_of(b).hist_small + 1, hints_of(b).hist_large + 1, hints_of(b).hist_copy + 1);
     stage_copy_alt(b);          // (staged result: the ALT section leaves behind the last ALT kernel)
     join_side(b);
     join_fourth(b);
@@ -1945,11 +1953,21 @@ void run_finalize(snf_batch_impl* b) {
 bool pass_graph_ok(snf_batch_impl* b) {
   const View& v = b->v;
   if (b->graph_mode == 1 && pacing_of(b).passes_in_flight.load() > 1) return false;      // (this batch itself is counted)
-  return b->graph_mode && !b->graph_failed && b->have_hist && b->fused && v.front && v.wave_path && !b->k.timeline && !b->time_all &&
+  return b->graph_mode && !b->graph_failed && hints_of(b).have_hist && b->fused && v.front && v.wave_path && !b->k.timeline && !b->time_all &&
          v.NS > 0 && !b->k.readprep_each_pass && !b->k.serial;
+}
+// A whole pass in execute mode with QC on returns the calls with `qc` set, and qc_sv fails every SINGLE_LEFT / SINGLE_RIGHT candidate
+// (SINGLE_BREAK, snf_stage_final.h) unless dev_output_candidates is set; rescue_phasing lifts nothing but MOSAIC_VAF.  Such a pass forms
+// no cluster of the two types.  Only here: snf_batch_call_candidates on its own - the two-call seam, a stage-0 fetch -
+// is still asked for the candidates, and so is every SNF_OUT_CANDIDATES pass.  SNF_OUT_ALL_CANDIDATES is the way to switch it off: the
+// same block with every candidate formed (callers that count the candidates; the A/B and the tests).
+bool pass_skips_single(const snf_batch_impl* b) {
+  return (b->v.out_mode & SNF_OUT_EXECUTE) && !(b->v.out_mode & SNF_OUT_ALL_CANDIDATES) && !b->cfg.no_qc && !b->cfg.dev_output_candidates;
 }
 void run_pass(snf_batch_impl* b) {
   View& v = b->v;
+  // (a function of the output mode and of what is fixed for the handle: the graph key below holds the output mode, and that is enough)
+  v.skip_single = pass_skips_single(b) ? 1 : 0;
   pass_begins(b);
   join_open_candidates(b);      // (before a replay or a capture: the wait is on events recorded outside either)
   if (!pass_graph_ok(b)) { run_call_candidates(b); run_finalize(b); return; }
@@ -1969,6 +1987,7 @@ void run_pass(snf_batch_impl* b) {
     // host-side state the two calls leave behind
     b->reads_ready = true; b->cov_avg_ready = true; b->finalized = true; b->finalize_runs = 1; b->res_current = true;
     b->rn_state = g.rn_state; v.rn_defer = g.rn_defer; v.out_valid = 1;
+    for (int k = 0; k < 3; k++) b->skipped_big[k] = g.skipped_big[k];
     return;
   }
   if (g.exec || g.passes < 2) { run_call_candidates(b); run_finalize(b); return; }    // eager: first pass of the configuration / timing pass
@@ -2009,6 +2028,7 @@ void run_pass(snf_batch_impl* b) {
     return;
   }
   g.graph = graph; g.exec = exec; g.rn_state = b->rn_state; g.rn_defer = v.rn_defer; g.cap_out = b->hb_out.cap; g.cap_alt = b->hb_alt.cap;
+  for (int k = 0; k < 3; k++) g.skipped_big[k] = b->skipped_big[k];
   if (v.prof) { size_t nn = 0; (void)hipGraphGetNodes(graph, nullptr, &nn); fprintf(stderr, "[SNF_PROF] pass graph: captured (%zu nodes)\n", nn); }
   SNF_HIP(hipGraphLaunch(g.exec, b->stream));
 }
@@ -2162,6 +2182,9 @@ void do_fetch(snf_batch_impl* b, int stage, snf_result_t* out) {
                     "fallback %lld alt bytes %lld fused bytes through the shared counter %llu (the rest in the waves' own slices; the split depends on scheduling, the total and the capacity do not) | ALT lists copy %llu small %llu large %llu/%llu/%llu/%llu thread %llu rows %llu\n", (long long)c.n_valid, (long long)c.n_occ, (long long)c.n_bins, (long long)c.n_seeds, (long long)c.n_clusters,
             (long long)c.n_rc, (long long)c.n_calls, (long long)c.n_cons, (long long)c.n_cons_reads, (long long)c.n_cons_fallback,
             (long long)c.alt_total, c.pool_extra_used, c.n_cls[0], c.n_cls[1], c.n_cls[2], c.n_cls[3], c.n_cls[4], c.n_cls[5], c.n_cls[6], c.n_cls[7]);
+    // (a pass with View::skip_single: seeds, clusters, refined and calls above are without the single-breakend types)
+    if (v.skip_single) fprintf(stderr, "[SNF_PROF] skip single: %llu of %lld waves of w4s_segment left early (every window of theirs a single-breakend one)\n",
+                               c.n_w4left, (long long)((v.N + 63) / 64));
     // the merge scan's own account (both counters start from zero with the rest of Counts: z0_init / enqueue_pass_init)
     fprintf(stderr, "[SNF_PROF] merge scan: %lld runs, %lld groups redone serially (run_gap %d)\n", (long long)c.n_runs, (long long)c.n_dirty_groups, (int)v.run_gap);
   }
@@ -2175,12 +2198,12 @@ void do_fetch(snf_batch_impl* b, int stage, snf_result_t* out) {
       bool skipped_work = false;
       for (int k = 0; k < 3; k++) {
         if (b->skipped_big[k] && c.n_big[k] > 0) skipped_work = true;
-        b->hist_big[k] = c.n_big[k];        // (refreshed first: the next pass of this handle launches what this one skipped)
+        hints_of(b).hist_big[k] = c.n_big[k];        // (refreshed first: the next pass of this handle launches what this one skipped)
       }
       if (skipped_work) { b->pass_idle = true; fail("internal: a pass skipped x_big although items were handed to it (the handle's next pass launches it)"); }
-      b->have_big_hist = true;
-      b->hist_small = (int64_t)c.n_cls[1]; b->hist_large = (int64_t)(c.n_cls[2] + c.n_cls[3] + c.n_cls[4] + c.n_cls[5]); b->hist_copy = (int64_t)c.n_cls[0];
-      b->hist_calls = c.n_calls; b->have_hist = true;
+      hints_of(b).have_big_hist = true;
+      hints_of(b).hist_small = (int64_t)c.n_cls[1]; hints_of(b).hist_large = (int64_t)(c.n_cls[2] + c.n_cls[3] + c.n_cls[4] + c.n_cls[5]); hints_of(b).hist_copy = (int64_t)c.n_cls[0];
+      hints_of(b).hist_calls = c.n_calls; hints_of(b).have_hist = true;
     }
     const OutHdr h = *v.res_out;
     const uint8_t* base = (const uint8_t*)b->hb_out.p;
@@ -2839,7 +2862,7 @@ int snf_batch_upload(snf_batch_t* bb) {
 int snf_batch_open(const snf_config_t* cfg, int device, const snf_task_input_t* tasks, int32_t n_tasks, int run, snf_batch_t** out) {
   if (out) *out = nullptr;
   if (!out || (n_tasks > 0 && !tasks) || n_tasks < 0) { g_err = "snf_batch_open: null argument"; return 1; }
-  if (run != SNF_RUN_NONE && run != SNF_RUN_CANDIDATES && !((run & SNF_RUN_PASS) && (run & ~SNF_RUN_PASS) <= (SNF_OUT_EXECUTE | SNF_OUT_DEVICE))) {
+  if (run != SNF_RUN_NONE && run != SNF_RUN_CANDIDATES && !((run & SNF_RUN_PASS) && (run & ~SNF_RUN_PASS) <= (SNF_OUT_EXECUTE | SNF_OUT_DEVICE | SNF_OUT_ALL_CANDIDATES))) {
     g_err = "snf_batch_open: unknown run mode"; return 1;
   }
   snf_batch_t* h = nullptr;
@@ -2893,6 +2916,7 @@ int snf_batch_call_candidates(snf_batch_t* bb) {
     auto b = reinterpret_cast<snf_batch_impl*>(bb);
     if (!b || !b->uploaded) fail("batch not uploaded");
     SNF_HIP(hipSetDevice(b->device));
+    b->v.skip_single = 0;      // (the candidates are asked for: run_pass alone sets it)
     run_call_candidates(b);
   })
 }
@@ -2954,7 +2978,7 @@ int snf_batch_set_output(snf_batch_t* bb, int mode) {
   SNF_TRY({
     auto b = reinterpret_cast<snf_batch_impl*>(bb);
     if (!b) fail("null batch");
-    if (mode < 0 || mode > (SNF_OUT_EXECUTE | SNF_OUT_DEVICE)) fail("unknown output mode");
+    if (mode < 0 || mode > (SNF_OUT_EXECUTE | SNF_OUT_DEVICE | SNF_OUT_ALL_CANDIDATES)) fail("unknown output mode");
     b->out_mode = mode; b->v.out_mode = mode;
   })
 }

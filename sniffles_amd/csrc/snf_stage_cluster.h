@@ -130,10 +130,10 @@ SNF_HD void a4_binstats_body(int64_t b, const View& v) {
     if (!lead_is_long(v, o)) n_normal++;
   }
   for (int h = 0; h < 3; h++) v.bin_hap[3 * b + h] = (uint16_t)hc[h];
-  bool el = n_normal >= v.cfg.dev_min_leads_cluster;
+  int g = key_grp(v.bin_key[b]);
+  bool el = n_normal >= v.cfg.dev_min_leads_cluster && !seed_type_skipped(v, g & 7);
   v.bin_elig[b] = el;
   v.eligflag[b] = el ? 1u : 0u;
-  int g = key_grp(v.bin_key[b]);
   if (b == 0 || key_grp(v.bin_key[b - 1]) != g) v.grp_first_bin[g] = (int32_t)b;
 }
 

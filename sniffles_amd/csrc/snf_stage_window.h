@@ -231,6 +231,25 @@ __global__ void __launch_bounds__(64) w4s_segment(const View v, int64_t n_unused
   if (lane < nw) wr = ((const uint4*)v.wlist)[k0 + lane];
   const int xlo = (int)((int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)wr.z) - B0);                 // owned positions: [xlo, xhi)
   const int xhi = (int)((int64_t)(uint32_t)__builtin_amdgcn_readlane((int)(wr.z + wr.y), nw - 1) - B0);   // <= 63 + CAP
+  // group and first bin of the lane's window
+  uint32_t wgrp = 0, wbin0 = 0;
+  if (lane < nw) {
+    const int t = (int)wr.w;
+    const int64_t o0 = v.t_win_off[t], nwin = (v.t_win_off[t + 1] - o0) / SNF_NTYPES, rem = (int64_t)wr.x - o0;
+    wgrp = (uint32_t)(t * 8 + (int)(rem / nwin)); wbin0 = (uint32_t)((rem % nwin) << v.win_bits);
+  }
+  // View::skip_single: a window of a single-breakend type yields no seed, no `leads` and no `leads_long`.  A wave that owns nothing else
+  // leaves here, in front of the key rows and the rank sort - whatever the size of its windows, so neither instance of the split form
+  // sees it again.  w6t_emit reads the word of every position: the wave's own positions get one without a flag (the words of another
+  // pass of this handle may lie there), and its three counts are zero.  The other positions below xhi belong to the wave before.
+  if (v.skip_single && !__ballot(lane < nw && !seed_type_skipped(v, (int)(wgrp & 7u)))) {
+    for (int x = lane; x < xhi; x += 64) if (x >= xlo) v.key_out[B0 + x] = 0;
+    if (lane == 0) {
+      v.ws_seeds[i] = 0; v.ws_nf[i] = 0; v.ws_nl[i] = 0;
+      if (v.prof) atomicAdd(&v.cnt->n_w4left, 1ull);
+    }
+    return;
+  }
   if (v.w4_mode == 1 && __shfl(wave_incl_max(lane < nw ? (int)wr.y : 0), 63, 64) > CAP) {
     // one of its windows holds more than CAP leads (the LDS rows and the pad behind the keys are sized for CAP): the large
     // instance's, through the list - at most as many blocks as the input has such windows
@@ -241,11 +260,7 @@ __global__ void __launch_bounds__(64) w4s_segment(const View v, int64_t n_unused
   wd[0] = w0;
 #pragma unroll
   for (int j = 1; j < E; j++) { const int x = lane + 64 * j; wd[j] = x < xhi ? v.key_in[B0 + x] : 0ull; }
-  if (lane < nw) {
-    const int t = (int)wr.w;
-    const int64_t o0 = v.t_win_off[t], nwin = (v.t_win_off[t + 1] - o0) / SNF_NTYPES, rem = (int64_t)wr.x - o0;
-    wS[lane] = (uint32_t)((int64_t)wr.z - B0); wG[lane] = (uint32_t)(t * 8 + (int)(rem / nwin)); wB[lane] = (uint32_t)((rem % nwin) << v.win_bits);
-  }
+  if (lane < nw) { wS[lane] = (uint32_t)((int64_t)wr.z - B0); wG[lane] = wgrp; wB[lane] = wbin0; }
 #pragma unroll
   for (int j = 0; j < E; j++) { const int x = lane + 64 * j; if (x < xhi) { sA[x] = 0; sB[x] = 0; widx[x] = 0; } }
   // what a rank loop reads behind the last window: it runs as far as the wave's largest window is long, from any window's start
@@ -342,7 +357,8 @@ __global__ void __launch_bounds__(64) w4s_segment(const View v, int64_t n_unused
       h = hpos[x];
       const uint32_t A = sA[h];
       all = (int)(A & 0xffffu); with_len = (int)(A >> 16);
-      const bool elig = with_len >= v.cfg.dev_min_leads_cluster;
+      // (a wave with windows of both kinds: the single-breakend ones were sorted and counted with the rest, their bins only seed nothing)
+      const bool elig = with_len >= v.cfg.dev_min_leads_cluster && !(v.skip_single && seed_type_skipped(v, (int)(wG[wkey_widx(sk[j])] & 7u)));
       f_norm = elig && !wkey_long(sk[j]); f_long = elig && wkey_long(sk[j]); f_seed = elig && x == h;
       f_null = x - h + 1 > v.cfg.consensus_max_reads_bin;      // leadprov.py:406-408 (counts every lead of the bin)
     }

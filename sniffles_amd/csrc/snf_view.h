@@ -23,6 +23,7 @@ struct Counts {
   int64_t max_win;           // ... and the largest window (only formed at upload: w2 with View::win_stats)
   int64_t n_big64;           // ... and the windows of more than 64 leads (upload): at most that many blocks need the large instance of w4s_segment
   unsigned long long n_w4big;       // blocks the small instance of w4s_segment handed on in this pass (View::w4_list)
+  unsigned long long n_w4left;      // (SNF_PROF only) waves of w4s_segment that left early: every window of theirs a single-breakend one (View::skip_single)
   int64_t n_cons_fallback;   // consensus calls that do not fit the LDS workgroup kernel
   unsigned long long cons_bytes[4]; // algorithmic bytes of the ALT stage per class (0 fallback, 1 small, 2 large, 3 copy)
   unsigned long long n_cls[8];      // ALT work lists: 0 verbatim copy, 1 SMALL, 2-5 LARGE by work (2 = heaviest), 6 thread-kernel fallback,
@@ -195,6 +196,9 @@ struct View {
   // occupied window ordered and binned by one wave.  Replaces the prefilter + sort + a2..a7 chain when `front` is set.
   int32_t front;              // 1: on
   int32_t win_bits;           // W
+  // 1 (set by run_pass only): this pass returns the execute block with QC on, which can never hold a SINGLE_LEFT / SINGLE_RIGHT call (qc_sv,
+  // snf_stage_final.h) - bins of the two types seed no cluster (seed_type_skipped below), so nothing behind the front end sees their leads
+  int32_t skip_single, _pad_ss;
   int64_t NW;                 // window slots of the batch (dense: per task SNF_NTYPES x windows of its contig)
   const int64_t* t_win_off;   // [T+1] first window of task t
   // The INDEX half (w1_hist .. w3_scatter: wbase, wlist, blk_k0 and the bucket array key_in) depends on the lead table, cluster_binsize
@@ -336,6 +340,10 @@ struct View {
   uint8_t* aln_kept_w;       // [N+1] kept flag per (call, other read) of the workgroup kernels, indexed like crl_*
   int64_t* crl_off; int32_t* crl_len;  // [<= N] pool offset / length of every 'other' read, in cluster order per call
 };
+
+// the one eligibility rule of View::skip_single, for the window front end (w4s_segment) and the sort path (a4_binstats_body) alike:
+// a bin of a single-breakend type (the last two of a task's groups) seeds nothing in such a pass
+SNF_HD bool seed_type_skipped(const View& v, int svtype) { return v.skip_single && svtype >= SNF_SINGLE_LEFT; }
 
 // measurement build (-DSNF_ITRACE): every workgroup of the kernels that carry IT_SCOPE(slot) leaves when it started and how long it
 // ran - what the device's occupancy over a kernel's span looks like (ramp, plateau, tail) and which workgroups are the last

@@ -48,7 +48,7 @@ class Task:
         the interpreter lock is released for all of it); every task has its own batch handle and streams.  The reference's worker
         processes get the same overlap from being several (`sniffles:495-530`).  Optional: a task that was not prepared does the same
         work when it is called."""
-        from .abi import OUT_CANDIDATES, OUT_EXECUTE
+        from .abi import OUT_ALL_CANDIDATES, OUT_CANDIDATES, OUT_EXECUTE
         if self._prep is not None or self._server() is not None:      # (through a GPU server the call itself hands the task over)
             return
         self._release()
@@ -56,7 +56,7 @@ class Task:
         from .soa import DeviceTaskInput
         if isinstance(self._ti, DeviceTaskInput):      # columns already in HBM: the call itself hands them over device-to-device
             return
-        run = lib.Batch.RUN_CANDIDATES if execute is None else (lib.Batch.RUN_PASS | (OUT_EXECUTE if execute else OUT_CANDIDATES))
+        run = lib.Batch.RUN_CANDIDATES if execute is None else (lib.Batch.RUN_PASS | (OUT_EXECUTE | OUT_ALL_CANDIDATES if execute else OUT_CANDIDATES))
         self._prep = {"mode": execute, "pending": lib.Batch.open_in_background(config, [self._ti], device=self.device, run=run)}
 
     def _prepared(self, execute) -> bool:
@@ -197,10 +197,11 @@ class Task:
         `config.sort`; parallel.py:265-271), filtered and ordered on the device.
         The arrays of the result are VIEWS of the batch's pinned block: they die with `close()` or the next call on this task
         (the buffer is handed to the next batch) - copy what has to outlive it."""
-        from .abi import OUT_CANDIDATES, OUT_EXECUTE
+        from .abi import OUT_ALL_CANDIDATES, OUT_CANDIDATES, OUT_EXECUTE
         if not self._prepared(bool(execute)):
             self._open(config)
-            self._batch.set_output(OUT_EXECUTE if execute else OUT_CANDIDATES)
+            # (every candidate is formed, also the single-breakend ones an execute block never holds: `self.sv_id` advances by their number)
+            self._batch.set_output(OUT_EXECUTE | OUT_ALL_CANDIDATES if execute else OUT_CANDIDATES)
             self._batch.run_pass()            # call_candidates + finalize (both only enqueue; the fetch is the one wait)
         res = self._batch.fetch(1, copy=False)
         if int(res.task_status[0]) == TASK_ERR_UNBOUND_END:
